@@ -25,7 +25,9 @@ Workloads (svsdf_amd/workload.py, BASELINE.json `configs`):
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (DESIGN.md "Measurement" explains every field).
+Rank 0 prints ONE JSON line (DESIGN.md "Measurement" explains every field).  With --dump-outputs DIR it also writes what
+the last timed step returned -- cost, gradT (N,), gradC (6N, 3), float64 -- as DIR/cost.npy, grad_T.npy, grad_coeffs.npy;
+the workload is seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import gc
@@ -40,10 +42,9 @@ for p in (ROOT, os.path.join(ROOT, "implicit-svsdf-planner_amd")):
         sys.path.insert(0, p)
 
 # The library can run a large shard as up to 4 point batches on their own HIP streams; streams that share one of the
-# runtime's hardware queues (default 4) serialise.  This is the HOST's setting: it must be in the
-# environment before the HIP runtime initialises, i.e. before `import torch`.  The library itself never touches it -- it
-# times 1 / 3 / 4 batches on the first evaluations after svsdf_set_points and keeps the fastest (svsdf_stats.batches).
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# runtime's hardware queues serialise.  The number of queues is the HOST's setting and bench.py leaves it
+# to the environment.  The library itself never touches it -- it times 1 / 3 / 4 batches on the first evaluations after
+# svsdf_set_points and keeps the fastest (svsdf_stats.batches).
 
 import numpy as np  # noqa: E402
 
@@ -78,6 +79,8 @@ def parse():
     ap.add_argument("--extra-steps", type=int, default=10)
     ap.add_argument("--sustained-steps", type=int, default=300, help="length of the `sustained` run (generic durations)")
     ap.add_argument("--only", default=None, help="run ONE sub-measurement and print its object: reference_scale")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (cost, gradT, gradC) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -177,7 +180,7 @@ class Runner:
         combine_ms = 0.0
         t0 = time.perf_counter()
         for _ in range(steps):
-            self.step()
+            self.out = self.step()
             last = self.ctx.stats()
             for k in acc:
                 acc[k] += last[k]
@@ -634,6 +637,18 @@ def stripe_report(r, devices, steps=5):
                     "ideal = slowest stripe + the fixed host cost"}
 
 
+def dump_outputs(d, out):
+    """What the caller of the timed path received from the last timed step: the accumulated cost and its gradients with
+    respect to the piece durations and the MINCO coefficients (float64, a few KB)."""
+    cost, gT, gC = out
+    arrays = {"cost": np.array([cost], dtype=np.float64), "grad_T": np.asarray(gT, dtype=np.float64),
+              "grad_coeffs": np.asarray(gC, dtype=np.float64)}
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    return {"dir": d, "arrays": {k: list(v.shape) for k, v in arrays.items()}}
+
+
 def main():
     a = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -691,6 +706,8 @@ def main():
     w, N, ctx = r.w, r.N, r.ctx
     setup = r.settle()
     elapsed, acc, last, combine_ms = r.timed(a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, r.out)
     prof_steps = max(1, min(a.steps, 5))
     solve_ms_step, dev_ms_step = r.profiled(prof_steps)
     r.fence()
@@ -803,6 +820,8 @@ def main():
         res["generic_durations"] = generic
         if not a.no_extras and a.steps >= 5:
             res["sustained"] = sustained(r, max(300, a.sustained_steps))
+    if a.dump_outputs:
+        res["dump_outputs"] = dumped
     res["evaluations_in_this_run"] = r.n_eval   # of the headline workload (settle + warm-up + timed + profiled + callbacks)
     if multi or devices is not None or ar_ms is not None:
         res["combine"] = {"ms_allreduce": ar_ms, "ms_combine_inprocess": combine_ms if a.inprocess else None,

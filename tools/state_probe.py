@@ -5,7 +5,7 @@ usage: python tools/state_probe.py [sequence ...]      (default: all)
 Every sequence runs in its OWN process; the NS block is the same in all of them: context, settle, 3 x 20 timed
 evaluations, one profiled evaluation (HIP-event device span, merged k_solve / k_round time), the shader clock the kernels
 measured themselves, the plan, free device memory.
-  alone        NS in a fresh process (GPU_MAX_HW_QUEUES=8 like bench.py)
+  alone        NS in a fresh process (the hardware-queue setting inherited from the environment, like bench.py)
   alone_q4     the same with the runtime's default number of hardware queues
   after_c3     C3 context: settle + 60 evaluations, closed; then NS
   beside_c3    C3 context kept open (idle) while NS runs
@@ -104,8 +104,6 @@ def main():
         env = dict(os.environ)
         if s == "alone_q4":
             env.pop("GPU_MAX_HW_QUEUES", None)
-        else:
-            env["GPU_MAX_HW_QUEUES"] = "8"
         try:
             out = subprocess.run([sys.executable, "-c", CHILD % dict(root=ROOT), s], env=env, stdout=subprocess.PIPE,
                                  stderr=subprocess.PIPE, timeout=300)
