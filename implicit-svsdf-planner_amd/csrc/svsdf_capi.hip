@@ -606,6 +606,22 @@ int svsdf_last_stats(const svsdf_ctx *ctx, svsdf_stats *out) {
   return SVSDF_OK;
 }
 
+int svsdf_last_launches(const svsdf_ctx *ctx, svsdf_launch_rec *out, int cap, int *count) {
+  if (!ctx || !count || cap < 0 || (cap > 0 && !out)) return SVSDF_ERR_INVALID;
+  if (!ctx->subs.empty()) return SVSDF_ERR_INVALID;   // multi-device contexts: per device, not recorded here
+  const size_t stride = cap > 0 ? (size_t)out->struct_size : sizeof(svsdf_launch_rec);
+  if (cap > 0 && stride < offsetof(svsdf_launch_rec, lds_bytes) + sizeof(out->lds_bytes)) return SVSDF_ERR_INVALID;   // older than version 1
+  const size_t bytes = std::min(stride, sizeof(svsdf_launch_rec));
+  const int n = std::min(cap, std::min(ctx->n_launches, (int)SVSDF_LAUNCH_REC_CAP));
+  for (int i = 0; i < n; ++i) {
+    svsdf_launch_rec r = ctx->launches[i];
+    r.struct_size = (int)bytes;
+    std::memcpy(reinterpret_cast<char *>(out) + (size_t)i * stride, &r, bytes);
+  }
+  *count = ctx->n_launches;
+  return SVSDF_OK;
+}
+
 // ---- host MINCO helpers --------------------------------------------------------------------------
 int svsdf_minco_coeffs(const double head_state[9], const double tail_state[9], int N, const double *inPs,
                        const double *T, double *coeffs) {

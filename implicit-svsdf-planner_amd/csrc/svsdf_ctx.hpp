@@ -200,6 +200,8 @@ struct svsdf_ctx {
   std::vector<std::pair<size_t, size_t>> round_events;   // k_round launches
   std::vector<std::pair<size_t, size_t>> tail_events;    // k_tail launches
   svsdf_stats stats{};
+  svsdf_launch_rec launches[SVSDF_LAUNCH_REC_CAP];   // launch record of the last evaluation (svsdf_last_launches)
+  int n_launches = 0;                                // launches of the last evaluation (beyond the array: counted only)
 
   // in-process multi-GPU group (svsdf_config::n_devices > 1): this context then owns no device state of its
   // own, only the host-side callback state below; subs[k] is the single-device context of stripe k
@@ -284,6 +286,19 @@ int choose_tail_iter(const svsdf_ctx *ctx);
 int swept_field(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, double *sdf_sorted);
 int evaluate_points(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bool allow_cull, bool with_partial);
 void fill_mode_stats(svsdf_ctx *ctx);
+// launch record: a fresh one per evaluation, one entry per launch (plain stores into the context's fixed array);
+// null when the array is full
+inline void reset_launches(svsdf_ctx *ctx) { ctx->n_launches = 0; }
+inline svsdf_launch_rec *record_launch(svsdf_ctx *ctx, int kernel, int shape, unsigned grid, unsigned block, size_t lds,
+                                       long long work, int batch) {
+  if (ctx->n_launches >= SVSDF_LAUNCH_REC_CAP) { ++ctx->n_launches; return nullptr; }   // beyond the array: counted only
+  svsdf_launch_rec *r = &ctx->launches[ctx->n_launches++];
+  *r = svsdf_launch_rec{};
+  r->struct_size = (int)sizeof(svsdf_launch_rec);
+  r->kernel = kernel; r->shape = shape; r->grid = grid; r->block = block; r->lds_bytes = lds; r->work = work; r->batch = batch;
+  return r;
+}
+int compiled_shape(int shape);
 int run_pipeline_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double *T);
 void accumulate(int N, const double *partial, double *cost, double *gradT, double *gradC);
 void shard_plan(const double *xyz, size_t P, int rk, int ws, int flags, std::vector<long long> &out);

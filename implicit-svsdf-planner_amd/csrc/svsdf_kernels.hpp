@@ -2208,7 +2208,9 @@ constexpr int kRoundBlock = SVSDF_ROUND_BLOCK;
                                  // walk it needs 134 (3 waves).  The allocator then spills ONE VGPR (8 - 20 B of scratch) and C4 gains 2.1 - 2.5 %
                                  // (500 k: 3.43 -> 3.36 ms, 4 M: 19.41 -> 18.93), but tests/test_gpu_plan.py::test_fused_tail_is_invisible aborts
                                  // with a device fault, like SVSDF_ROUND_WAVES=5 did: these kernels keep ~ 200 spilled SGPRs in VGPR lanes, and a
-                                 // VGPR spilled to scratch under a partial EXEC mask is the suspect.  No variant of k_round with scratch is shipped.
+                                 // VGPR spilled to scratch under a partial EXEC mask is the suspect.  No variant of k_round that addresses scratch is
+                                 // shipped: k_round<Polygon, 8 lanes, MODE 1 .. 3> (edges in global memory) reserve 8 B that no instruction touches
+                                 // (a dead spill slot + the scavenger's emergency slot; tests/test_kernel_resources.py holds exactly that).
 #endif
 #ifndef SVSDF_ROUND_WAVES
 #define SVSDF_ROUND_WAVES 1   // waves per SIMD the register allocation of k_round aims at (1: whatever its registers allow = 4).  Round 6
@@ -2450,9 +2452,10 @@ __device__ __forceinline__ void tail_solve_pass(const TrajL &tr, const double *_
 #define SVSDF_TAIL_WAVES 3   // waves per SIMD the register allocation aims at (168 VGPRs)
 #endif
 // WAVES: waves per SIMD the register allocation aims at.  3 (168 VGPRs) is what a cloud of thousands of points wants -- and
-// costs ~ 100 spilled VGPRs (300 - 400 B of scratch per lane).  A launch with a wave slot for every point at TWO waves per
+// costs 82 - 173 spilled VGPRs (260 - 420 B of scratch per lane).  A launch with a wave slot for every point at TWO waves per
 // SIMD (<= 2048 points on 256 CUs: the reference's own scale) is a chain of dependent steps of single waves, where a scratch
-// round trip is pure latency: kTailLatencyWaves = 2 lets the kernel keep its ~ 240 VGPRs, no scratch (end of round 6:
+// round trip is pure latency: kTailLatencyWaves = 2 lets the kernel keep its ~ 240 VGPRs, without scratch for the analytic
+// shapes; the two Polygon ids spill 2 VGPRs (12 B) in the scanning modes 1 .. 3 (tests/test_kernel_resources.py; end of round 6:
 // reference-scale callbacks - 4 ... - 5 %, 3 k-point clouds - 1.5 %; 10 k points + 2 % -- hence two instantiations,
 // chosen per launch: launch_tail).
 constexpr int kTailLatencyWaves = 2;

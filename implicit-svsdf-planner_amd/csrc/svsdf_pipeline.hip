@@ -206,8 +206,13 @@ void launch_solve(svsdf_ctx *ctx, int G, hipStream_t st, const QuerySet &qs, lon
   const double *d_rot = d_tk + ctx->K + (ctx->K + kChunk - 1) / kChunk;
   const SolveLaunch a{ctx->d_traj, d_tk, ctx->d_pose, ctx->d_chunks, ctx->sp, qs, out_sdf, out_t, ctx->prune | (solo ? 2 : 0), ctl, work_idx, cull_thresh,
                       cull2 ? d_rot : nullptr, ctx->slack_max};
-  if (!launch_k_solve(poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id, G, grid, (unsigned)blk, lds_total, st, a) && ctx->launch_err.empty())
+  const int shape = poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
+  if (!launch_k_solve(shape, G, grid, (unsigned)blk, lds_total, st, a) && ctx->launch_err.empty())
     ctx->launch_err = "k_solve: shape not compiled into this build";
+  if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_SOLVE, compiled_shape(shape), grid, (unsigned)blk, lds_total, max_queries,
+                                          (int)(ctl - ctx->d_ctl))) {
+    r->targ[0] = G; r->targ[1] = 1; r->iter = work_idx; r->solo = solo ? 1 : 0;
+  }
   debug_sync(st, "k_solve", G, work_idx);
   if (ctx->profile) {
     e1 = next_event(ctx);
@@ -251,8 +256,12 @@ void launch_round(svsdf_ctx *ctx, hipStream_t st, int b, int it) {
                       band_delta, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy, ctx->d_ctl + b, ctx->round_list | ((ctx->scan_anchors && ctx->lipschitz_ok) ? 16 : 0)};
   size_t e0 = 0, e1 = 0;
   if (ctx->profile) { e0 = next_event(ctx); (void)hipEventRecord(ctx->ev_pool[e0], st); }
-  if (!launch_k_round(poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id, lp, mode, grid, lds, st, a) && ctx->launch_err.empty())
+  const int shape = poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
+  if (!launch_k_round(shape, lp, mode, grid, lds, st, a) && ctx->launch_err.empty())
     ctx->launch_err = "k_round: shape not compiled into this build";
+  if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_ROUND, compiled_shape(shape), grid, (unsigned)kRoundBlock, lds, pts, b)) {
+    r->targ[0] = lp; r->targ[1] = mode; r->iter = it; r->anchors = (a.clist_on & 16) ? 1 : 0;
+  }
   debug_sync(st, "k_round", lp * 10 + mode, it);
   if (ctx->profile) {
     e1 = next_event(ctx);
@@ -307,8 +316,13 @@ void launch_tail(svsdf_ctx *ctx, hipStream_t st, int b, int it0) {
                      (ctx->tail_latency && ppw == 1 && pts <= (long long)ctx->n_cu * 4 * svsdf::kTailLatencyWaves) ? 1 : 0};
   size_t e0 = 0, e1 = 0;
   if (ctx->profile) { e0 = next_event(ctx); (void)hipEventRecord(ctx->ev_pool[e0], st); }
-  if (!launch_k_tail(poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id, mode, grid, lds, st, a) && ctx->launch_err.empty())
+  const int shape = poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
+  if (!launch_k_tail(shape, mode, grid, lds, st, a) && ctx->launch_err.empty())
     ctx->launch_err = "k_tail: shape not compiled into this build";
+  if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_TAIL, compiled_shape(shape), grid, (unsigned)kTailBlock, lds, pts, b)) {
+    r->targ[0] = mode; r->targ[1] = a.latency ? svsdf::kTailLatencyWaves : SVSDF_TAIL_WAVES; r->iter = it0; r->points_per_wave = ppw;
+    r->local_state = local ? 1 : 0; r->duo = (ppw == 1 && ctx->tail_duo) ? 1 : 0; r->anchors = (a.clist_on & 16) ? 1 : 0;
+  }
   debug_sync(st, "k_tail", mode, it0);
   if (ctx->profile) {
     e1 = next_event(ctx);
@@ -344,6 +358,7 @@ void launch_classify(svsdf_ctx *ctx, hipStream_t st, int b) {
   const ClassifyLaunch a{ctx->d_traj, ctx->sp, ctx->d_px, ctx->d_py, ctx->d_sdf, ctx->d_t, ctx->d_res_sdf, ctx->d_res_t,
                          ctx->d_res_gx, ctx->d_res_gy, ctx->gs, ctx->d_ctl + b, &ctx->d_ctl->n_int, (int)ctx->icap};
   (void)launch_k_classify(ctx->cfg.shape_id, grid, lds, st, a);
+  (void)record_launch(ctx, SVSDF_KERNEL_CLASSIFY, compiled_shape(ctx->cfg.shape_id), grid, (unsigned)kBlock, lds, ctx->bcount[b], b);
   debug_sync(st, "k_classify", b, 0);
 }
 
@@ -472,6 +487,7 @@ int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bo
   hipLaunchKernelGGL(k_prep, dim3(1), dim3(1024), lds, ctx->stream, ctx->d_in, N, dur, (int)K,
                      ctx->piece_time_mode, ctx->d_traj,
                      ctx->d_pose, ctx->d_chunks, ctx->r_bound, ctx->d_ctl, ctx->nbatch, clear_nonfinite ? ctx->d_nonfinite : nullptr);
+  (void)record_launch(ctx, SVSDF_KERNEL_PREP, -1, 1, 1024, lds, (long long)K, 0);
   return SVSDF_OK;
 }
 
@@ -539,6 +555,7 @@ int enqueue_queries(svsdf_ctx *ctx, int N, const double *coeffs, const double *T
   ctx->tail_events.clear();
   ctx->stats = svsdf_stats{};
   ctx->stats.points = ctx->P;
+  reset_launches(ctx);
   const size_t e_begin = next_event(ctx);
   (void)hipEventRecord(ctx->ev_pool[e_begin], ctx->stream);
   int rc = upload_traj(ctx, N, coeffs, T, /*clear_nonfinite=*/true);   // (k_prep also clears the non-finite counter)
@@ -584,6 +601,7 @@ int swept_field(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, do
   ctx->tail_events.clear();
   ctx->stats = svsdf_stats{};
   ctx->stats.points = ctx->P;
+  reset_launches(ctx);
   int rc = upload_traj(ctx, N, coeffs, T);
   if (rc) return rc;
   if (ctx->nbatch > 1) HIPCHK(hipEventRecord(ctx->ev_prep, ctx->stream));
@@ -627,11 +645,14 @@ int reduce_and_read(svsdf_ctx *ctx, bool with_partial) {
                        (int)ctx->P, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
                        ctx->cfg.safety_hor, ctx->cfg.weight_p, ctx->d_block_partials, ctx->d_nonfinite, ctx->d_out,
                        ctx->d_ctl, ctx->nbatch, ctx->it_done, (int)kOutPartial, (int)kOutDoubles, ctx->d_ticket, ctx->h_out_dev, fuse);
+    if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_REDUCE, -1, grid, (unsigned)kBlock, lds, (long long)ctx->P, 0)) r->fused = fuse;
     if (!fuse) {
       hipLaunchKernelGGL(k_final, dim3((unsigned)plen), dim3(64), 0, ctx->stream, ctx->d_block_partials, (int)grid, ctx->d_sums);
+      (void)record_launch(ctx, SVSDF_KERNEL_FINAL, -1, (unsigned)plen, 64, 0, (long long)grid, 0);
       hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, ctx->stream, ctx->d_sums, N, ctx->d_out, ctx->d_ctl,
                          ctx->nbatch, ctx->it_done, ctx->d_nonfinite,
                          reinterpret_cast<unsigned long long *>(ctx->d_out + kOutPartial), ctx->h_out_dev, (int)kOutDoubles);
+      (void)record_launch(ctx, SVSDF_KERNEL_FINISH, -1, 1, (unsigned)kBlock, 0, 0, 0);
     }
     host_written = ctx->h_out_dev != nullptr;
   } else {
@@ -639,6 +660,7 @@ int reduce_and_read(svsdf_ctx *ctx, bool with_partial) {
     hipLaunchKernelGGL(k_finish, dim3(1), dim3(kBlock), 0, ctx->stream, ctx->d_sums, N, ctx->d_out, ctx->d_ctl,
                        ctx->nbatch, ctx->it_done, ctx->d_nonfinite,
                        reinterpret_cast<unsigned long long *>(ctx->d_out + kOutPartial), ctx->h_out_dev, (int)kOutDoubles);
+    (void)record_launch(ctx, SVSDF_KERNEL_FINISH, -1, 1, (unsigned)kBlock, 0, 0, 0);
     host_written = ctx->h_out_dev != nullptr;
   }
   ctx->e_end = next_event(ctx);
@@ -792,6 +814,7 @@ int run_pipeline_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double 
     std::memset(ctx->h_out, 0, kOutDoubles * sizeof(double));
     ctx->N = N;
     ctx->stats = svsdf_stats{};
+    reset_launches(ctx);
     fill_mode_stats(ctx);
     ctx->h_partial = ctx->h_out;
     return SVSDF_OK;

@@ -31,6 +31,7 @@ EXPORTS = [
     "svsdf_mesh_outline", "svsdf_mesh_outline_obj", "svsdf_swept_outline", "svsdf_outline_extrude",
     "svsdf_get_plan", "svsdf_set_plan", "svsdf_set_combine", "svsdf_group_info", "svsdf_debug_sdf_at",
     "svsdf_group_stripe", "svsdf_set_group_serial", "svsdf_shape_selfcheck", "svsdf_mesh_section", "svsdf_mesh_section_obj",
+    "svsdf_last_launches",
 ]
 
 
@@ -79,6 +80,18 @@ class Plan(C.Structure):
 
 
 PLAN_AUTO = -1
+
+
+class LaunchRec(C.Structure):
+    """svsdf_launch_rec (include/svsdf_c.h): one device launch of the last evaluation."""
+    _fields_ = [("struct_size", C.c_int), ("kernel", C.c_int), ("shape", C.c_int), ("targ", C.c_int * 3), ("iter", C.c_int),
+                ("batch", C.c_int), ("solo", C.c_int), ("points_per_wave", C.c_int), ("local_state", C.c_int),
+                ("duo", C.c_int), ("anchors", C.c_int), ("fused", C.c_int), ("work", C.c_longlong), ("grid", C.c_uint),
+                ("block", C.c_uint), ("lds_bytes", C.c_ulonglong)]
+
+
+LAUNCH_REC_CAP = 512     # SVSDF_LAUNCH_REC_CAP
+KERNELS = ["prep", "solve", "classify", "round", "tail", "reduce", "final", "finish"]   # svsdf_kernel_kind
 
 
 class OutlineStats(C.Structure):
@@ -139,6 +152,7 @@ def lib():
     L.svsdf_backward_T.argtypes = [_dp, _dp, C.c_int]
     L.svsdf_query_points.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]
     L.svsdf_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
+    L.svsdf_last_launches.argtypes = [C.c_void_p, C.POINTER(LaunchRec), C.c_int, C.POINTER(C.c_int)]
     L.svsdf_shard_indices.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     L.svsdf_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.svsdf_shard_plan.argtypes = [_dp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong),
@@ -718,6 +732,24 @@ class SvsdfContext:
 
     def set_profiling(self, enable=True):
         self._chk(self.L.svsdf_set_profiling(self.ctx, int(enable)), "svsdf_set_profiling")   # 2: serialised batches
+
+    def last_launches(self):
+        """Launch record of the last evaluation (svsdf_last_launches): one dict per device launch, in launch order, with
+        `kernel` as a name ("solve", "round", "tail", ...) and `targ` as a tuple of the template arguments.  Raises when
+        the evaluation made more launches than the library records."""
+        recs = (LaunchRec * LAUNCH_REC_CAP)()
+        recs[0].struct_size = C.sizeof(LaunchRec)
+        n = C.c_int(0)
+        self._chk(self.L.svsdf_last_launches(self.ctx, recs, LAUNCH_REC_CAP, C.byref(n)), "svsdf_last_launches")
+        if n.value > LAUNCH_REC_CAP:
+            raise SvsdfError(f"svsdf_last_launches: {n.value} launches, {LAUNCH_REC_CAP} recorded")
+        out = []
+        for r in recs[:n.value]:
+            d = {k: getattr(r, k) for k, _ in LaunchRec._fields_ if k != "struct_size"}
+            d["kernel"] = KERNELS[r.kernel]
+            d["targ"] = tuple(r.targ)
+            out.append(d)
+        return out
 
     def stats(self):
         s = Stats()

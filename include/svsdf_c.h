@@ -410,6 +410,47 @@ typedef struct svsdf_stats {
 } svsdf_stats;
 int svsdf_last_stats(const svsdf_ctx *ctx, svsdf_stats *out);
 
+/* Launch record of the last evaluation: which kernel instantiation every device launch of it ran, with what the launch
+ * decided at run time.  Tests use it to prove which instantiation a configuration reaches instead of inferring it from
+ * the size rules.  The library fills a fixed array per evaluation (no allocation); launches beyond
+ * SVSDF_LAUNCH_REC_CAP are counted but not recorded. */
+#define SVSDF_LAUNCH_REC_CAP 512
+enum svsdf_kernel_kind {
+  SVSDF_KERNEL_PREP = 0,      /* k_prep: pose table, chunk bounds and anchors */
+  SVSDF_KERNEL_SOLVE = 1,     /* k_solve<shape, G>: argmin solves (main points or selected GSIP samples) */
+  SVSDF_KERNEL_CLASSIFY = 2,  /* k_classify<shape>: exterior gradient / GSIP initialisation */
+  SVSDF_KERNEL_ROUND = 3,     /* k_round<shape, LP, MODE>: one GSIP iteration of the launch chain */
+  SVSDF_KERNEL_TAIL = 4,      /* k_tail<shape, MODE, WAVES>: every GSIP iteration from `iter` on */
+  SVSDF_KERNEL_REDUCE = 5,    /* k_reduce: assembly of the per-point terms (+ final sum when `fused`) */
+  SVSDF_KERNEL_FINAL = 6,     /* k_final: fixed-order sum of the block partials */
+  SVSDF_KERNEL_FINISH = 7     /* k_finish: suffix sum and counters */
+};
+typedef struct svsdf_launch_rec {
+  int struct_size;      /* bytes of this record the library wrote (see svsdf_last_launches) */
+  int kernel;           /* svsdf_kernel_kind */
+  int shape;            /* compiled shape id the kernel is specialised for: 0 ... 16, 17 = Polygon with its edges in LDS;
+                           -1 for the shape-independent kernels */
+  int targ[3];          /* template arguments: solve {G, 1, 0}; round {LP, MODE, 0}; tail {MODE, WAVES, 0}; else 0 */
+  int iter;             /* solve: work index (0 main solve, i + 1 the samples of GSIP iteration i); round / tail: GSIP
+                           iteration (tail: the first one); else 0 */
+  int batch;            /* point batch (stream) of the launch; 0 for the main-stream kernels */
+  int solo;             /* solve: one query per wave (fused pass) */
+  int points_per_wave;  /* tail: points a wave owns (1 or 2) */
+  int local_state;      /* tail: the GSIP state of the wave's points is kept in LDS */
+  int duo;              /* tail: with one point per wave, both half-waves own it */
+  int anchors;          /* round / tail: seed scans evaluate the anchors first */
+  int fused;            /* reduce: one launch assembles and sums (no k_final / k_finish) */
+  long long work;       /* queries (solve), points (round, tail, classify, reduce) the grid was sized for */
+  unsigned int grid, block;
+  unsigned long long lds_bytes;   /* dynamic LDS per block */
+} svsdf_launch_rec;
+/* Copies up to `cap` records of the last evaluation (svsdf_eval_penalty, svsdf_query_points, a callback, ...) into `out`
+ * and sets *count to the number of launches that evaluation made -- more than SVSDF_LAUNCH_REC_CAP when some were not
+ * recorded.  When cap > 0, out[0].struct_size must hold the caller's sizeof(svsdf_launch_rec): records are written with
+ * that stride, each truncated to the smaller of the two sizes, so that the record can grow.  Single-device contexts only
+ * (a multi-device context returns SVSDF_ERR_INVALID). */
+int svsdf_last_launches(const svsdf_ctx *ctx, svsdf_launch_rec *out, int cap, int *count);
+
 /* Launch plan of the resident point set.  Every field only moves TIME: each setting returns the same bits (cost, gradient
  * and per-point results).  By default everything follows deterministic rules: the first evaluation
  * after svsdf_set_points runs with the cheap GSIP bound and decides the bound mode from its counters, the batch count

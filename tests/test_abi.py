@@ -78,3 +78,21 @@ def test_set_conditions_on_a_host_only_context(built):
     import pytest
     with pytest.raises(svsdf_amd.SvsdfError):
         ctx.set_conditions(bad, w["tail_state"])
+
+
+def test_launch_record_abi_on_a_host_only_context(built):
+    """svsdf_last_launches: nothing recorded before an evaluation; the caller's struct_size sets the stride, and a size
+    below the first version of the record is refused."""
+    import ctypes as C
+    import svsdf_amd
+    from svsdf_amd import binding
+    ctx = svsdf_amd.SvsdfContext(shape="star", flags=svsdf_amd.FLAG_HOST_ONLY)
+    assert ctx.last_launches() == []
+    L = svsdf_amd.lib()
+    n = C.c_int(-1)
+    assert L.svsdf_last_launches(ctx.ctx, None, 0, C.byref(n)) == 0 and n.value == 0
+    recs = (binding.LaunchRec * 2)()
+    recs[0].struct_size = 8
+    assert L.svsdf_last_launches(ctx.ctx, recs, 2, C.byref(n)) == 1          # SVSDF_ERR_INVALID
+    assert L.svsdf_last_launches(None, recs, 2, C.byref(n)) == 1
+    assert C.sizeof(binding.LaunchRec) == 80
