@@ -8,8 +8,8 @@ BEO:774-869) over the whole query-point cloud, points already resident in HBM, t
 Workloads (svsdf_amd/workload.py, BASELINE.json `configs`):
   --gpus 1 (default)  C3 = configs[2]: sdHorseshoe, 32-piece MINCO, 1 M corridor query points -- the largest
                       single-GPU configuration (BASELINE.json quotes its metric on no particular config).
-                      The same line carries, as sub-objects measured in the same run: "north_star" (star,
-                      16 pieces, 1 M points: the workload BASELINE.json's north_star target is quoted on),
+                      With --full the same line carries, as sub-objects measured in the same run: "north_star"
+                      (star, 16 pieces, 1 M points: the workload BASELINE.json's north_star target is quoted on),
                       "map_distribution" (the headline config on the map-uniform cloud) and the
                       full-callback time (a14: MINCO forward + penalty + adjoint).
   --gpus N > 1        C4 = configs[3]: sdHeart, 32 pieces, 4 M points in total, striped over the N GPUs
@@ -22,8 +22,14 @@ Workloads (svsdf_amd/workload.py, BASELINE.json `configs`):
                                                            visible unless --devices repeats ordinals on purpose.
   --config / --points / --dist override the workload (C1..C5, NS).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, settles the launch plan, warms up, times the K steps and prints the headline line (config, setup and
+the counters of the timed steps included).  --full adds everything else this file measures, after the timed steps: the
+per-kernel roofline passes, full-callback and generic-duration timings, the sustained run, the sub-runs of other
+workloads, the reference-scale callbacks, the CPU baseline, and for N > 1 the combine A/B, the per-stripe report, the
+all-reduce alone and the one-GPU base; --no-extras / --no-cpu-baseline trim a --full run.
 
 Rank 0 prints ONE JSON line (DESIGN.md "Measurement" explains every field).  With --dump-outputs DIR it also writes what
 the last timed step returned -- cost, gradT (N,), gradC (6N, 3), float64 -- as DIR/cost.npy, grad_T.npy, grad_coeffs.npy;
@@ -73,11 +79,14 @@ def parse():
     ap.add_argument("--devices", default=None, help="comma list of HIP ordinals for --inprocess (default 0..N-1; "
                     "an ordinal may repeat to emulate several stripes on one GPU)")
     ap.add_argument("--combine", default="auto", choices=["auto", "host", "rccl"])
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline budget (rank 0, 1 GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the north_star / map_distribution sub-runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other measurement (roofline passes, callbacks, generic "
+                         "durations, sustained run, sub-runs, reference scale, CPU baseline, multi-GPU reports)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU-baseline budget (rank 0, 1 GPU; --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the sustained run and the sub-runs")
     ap.add_argument("--extra-steps", type=int, default=10)
-    ap.add_argument("--sustained-steps", type=int, default=300, help="length of the `sustained` run (generic durations)")
+    ap.add_argument("--sustained-steps", type=int, default=300, help="length of the `sustained` run (generic durations; --full)")
     ap.add_argument("--only", default=None, help="run ONE sub-measurement and print its object: reference_scale")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (cost, gradT, gradC) as DIR/<name>.npy")
@@ -708,19 +717,23 @@ def main():
     elapsed, acc, last, combine_ms = r.timed(a.steps, a.warmup)
     if a.dump_outputs and rank == 0:
         dumped = dump_outputs(a.dump_outputs, r.out)
-    prof_steps = max(1, min(a.steps, 5))
-    solve_ms_step, dev_ms_step = r.profiled(prof_steps)
-    r.fence()
-    cb_steps = max(1, min(a.steps, 10))
-    full_cb_ms = r.full_callback(cb_steps)
-    full_cb_pert_ms = r.full_callback(cb_steps, perturb=1e-3)
-    generic = r.generic_durations(max(1, min(a.steps, 20))) if not (tdist is not None or (a.inprocess and a.gpus > 1)) else None
+    generic = None
+    if a.full:
+        prof_steps = max(1, min(a.steps, 5))
+        solve_ms_step, dev_ms_step = r.profiled(prof_steps)
+        r.fence()
+        cb_steps = max(1, min(a.steps, 10))
+        full_cb_ms = r.full_callback(cb_steps)
+        full_cb_pert_ms = r.full_callback(cb_steps, perturb=1e-3)
+        if not (tdist is not None or (a.inprocess and a.gpus > 1)):
+            generic = r.generic_durations(max(1, min(a.steps, 20)))
     shard_points = last["points"]          # points resident on this process' device(s)
     evals_rank, interior_rank = acc["sdf_evals"], last["interior_points"]
     ar_ms = None
     if tdist is not None:
         if backend == "nccl":
-            ar_ms = allreduce_ms(tdist, 19 * N + 1)
+            if a.full:
+                ar_ms = allreduce_ms(tdist, 19 * N + 1)
             t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
             tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
             agg = torch.tensor([acc["sdf_evals"], acc["solves"], last["interior_points"], acc["scan_evals"],
@@ -745,19 +758,7 @@ def main():
 
     ms_per_step = 1e3 * elapsed / a.steps
     value = P_total * a.steps / elapsed
-    # dominant kernel = k_solve: rank-0 (in-process: slowest device) HIP-event time on the library's own streams
     pts_dev = shard_points / (n_gpus if a.inprocess and multi else 1)
-    ach_gbs = BYTES_PER_POINT * pts_dev / (solve_ms_step * 1e-3) / 1e9
-    fp64 = fp64_accounting(acc, a.steps, solve_ms_step, r.solve_ms_serial, r.round_ms, r.round_ms_serial, ms_per_step,
-                           ndev=(n_gpus if a.inprocess and multi else 1))
-    traffic = None
-    traffic_total = None
-    try:  # PMC-derived HBM traffic of k_solve per evaluation (collected offline, see profiles/)
-        tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
-        traffic = tr.get(f"{name}:{a.dist}:{int(pts_dev)}")
-        traffic_total = tr.get(f"{name}:{a.dist}:{int(pts_dev)}:total")
-    except Exception:
-        pass
     if multi:
         how = (f"ONE process, {n_gpus} devices {devices} through the C ABI's multi-device context, "
                f"{['host', 'host', 'rccl'][last['combine']]} combine of the partials"
@@ -779,37 +780,52 @@ def main():
                    "gsip_samples_per_point_rank0": acc["gsip_samples"] / a.steps / max(shard_points, 1),
                    "parallelism": f"points striped over {n_gpus} GPU(s) ({how}); one sum of {19 * N + 1} f64 per evaluation"},
         "setup": setup,
-        "full_callback_ms": full_cb_ms,
-        "full_callback_perturbed_ms": full_cb_pert_ms,
-        "full_callback_note": "a14 = costFunctionLmbmParallel: tau -> T, host MINCO forward, penalty (this bench's step), "
-                              "MINCO adjoint, chain rule; mean of %d calls.  'perturbed': every call gets x * (1 + 1e-3 * "
-                              "N(0,1)), i.e. the launch plan learned from the previous call is slightly off, as in a "
-                              "real optimisation" % cb_steps,
-        "roofline": {"bound": "hbm", "kernel": "k_solve (argmin over t: pruned table scan + scan layers 2-4 + descent; all launches of one evaluation)",
-                     "achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach_gbs / HBM_PEAK_GBS,
-                     "traffic": traffic,
-                     "traffic_total": traffic_total,
-                     "traffic_unit": "bytes per evaluation (2*FETCH_SIZE + WRITE_SIZE, separate rocprofv3 --pmc passes); `traffic` = the dominant "
-                                     "kernel k_solve alone, `traffic_total` = every kernel of the evaluation (k_prep ... k_finish; most of it is "
-                                     "k_round's hand-off of GSIP samples through HBM)",
-                     "kernel_ms_per_step": solve_ms_step, "kernel_ms_sum_per_step": r.solve_ms_sum,
-                     "kernel_time_note": "a large shard runs as several point batches on concurrent streams (setup.batches): kernel_ms_per_step = time "
-                                         "during which at least one k_solve launch was executing (merged HIP-event intervals; "
-                                         "what `achieved` divides by), kernel_ms_sum_per_step = plain sum of the launch durations "
-                                         "(what a rocprofv3 kernel trace adds up: launches x average duration)",
-                     "kernel_ms_serialized_per_step": r.solve_ms_serial, "device_ms_serialized_per_step": r.dev_ms_serial,
-                     "serialized_note": "the same evaluation with the batches run one after the other (svsdf_set_profiling 2; "
-                                        "what `SVSDF_BATCHES=1` gives): k_solve's own cost per evaluation, comparable with a "
-                                        "kernel trace taken that way (profiles/*_b1_kernel_stats.csv) and with round 1",
-                     "launches_per_step": acc["solve_launches"] / a.steps,
-                     "device_ms_per_step": dev_ms_step, "profiled_steps": prof_steps,
-                     "note": "24 B/point algorithmic; the solve is FP64-VALU bound (SURVEY.md §8d), see fp64",
-                     "k_round_ms_per_step": r.round_ms, "k_round_ms_sum_per_step": r.round_ms_sum,
-                     "k_round_ms_serialized_per_step": r.round_ms_serial,
-                     "fp64": fp64},
     }
+    if a.full:
+        # dominant kernel = k_solve: rank-0 (in-process: slowest device) HIP-event time on the library's own streams
+        ach_gbs = BYTES_PER_POINT * pts_dev / (solve_ms_step * 1e-3) / 1e9
+        fp64 = fp64_accounting(acc, a.steps, solve_ms_step, r.solve_ms_serial, r.round_ms, r.round_ms_serial, ms_per_step,
+                               ndev=(n_gpus if a.inprocess and multi else 1))
+        traffic = None
+        traffic_total = None
+        try:  # PMC-derived HBM traffic of k_solve per evaluation (collected offline, see profiles/)
+            tr = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
+            traffic = tr.get(f"{name}:{a.dist}:{int(pts_dev)}")
+            traffic_total = tr.get(f"{name}:{a.dist}:{int(pts_dev)}:total")
+        except Exception:
+            pass
+        res.update({
+            "full_callback_ms": full_cb_ms,
+            "full_callback_perturbed_ms": full_cb_pert_ms,
+            "full_callback_note": "a14 = costFunctionLmbmParallel: tau -> T, host MINCO forward, penalty (this bench's step), "
+                                  "MINCO adjoint, chain rule; mean of %d calls.  'perturbed': every call gets x * (1 + 1e-3 * "
+                                  "N(0,1)), i.e. the launch plan learned from the previous call is slightly off, as in a "
+                                  "real optimisation" % cb_steps,
+            "roofline": {"bound": "hbm", "kernel": "k_solve (argmin over t: pruned table scan + scan layers 2-4 + descent; all launches of one evaluation)",
+                         "achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach_gbs / HBM_PEAK_GBS,
+                         "traffic": traffic,
+                         "traffic_total": traffic_total,
+                         "traffic_unit": "bytes per evaluation (2*FETCH_SIZE + WRITE_SIZE, separate rocprofv3 --pmc passes); `traffic` = the dominant "
+                                         "kernel k_solve alone, `traffic_total` = every kernel of the evaluation (k_prep ... k_finish; most of it is "
+                                         "k_round's hand-off of GSIP samples through HBM)",
+                         "kernel_ms_per_step": solve_ms_step, "kernel_ms_sum_per_step": r.solve_ms_sum,
+                         "kernel_time_note": "a large shard runs as several point batches on concurrent streams (setup.batches): kernel_ms_per_step = time "
+                                             "during which at least one k_solve launch was executing (merged HIP-event intervals; "
+                                             "what `achieved` divides by), kernel_ms_sum_per_step = plain sum of the launch durations "
+                                             "(what a rocprofv3 kernel trace adds up: launches x average duration)",
+                         "kernel_ms_serialized_per_step": r.solve_ms_serial, "device_ms_serialized_per_step": r.dev_ms_serial,
+                         "serialized_note": "the same evaluation with the batches run one after the other (svsdf_set_profiling 2; "
+                                            "what `SVSDF_BATCHES=1` gives): k_solve's own cost per evaluation, comparable with a "
+                                            "kernel trace taken that way (profiles/*_b1_kernel_stats.csv) and with round 1",
+                         "launches_per_step": acc["solve_launches"] / a.steps,
+                         "device_ms_per_step": dev_ms_step, "profiled_steps": prof_steps,
+                         "note": "24 B/point algorithmic; the solve is FP64-VALU bound (SURVEY.md §8d), see fp64",
+                         "k_round_ms_per_step": r.round_ms, "k_round_ms_sum_per_step": r.round_ms_sum,
+                         "k_round_ms_serialized_per_step": r.round_ms_serial,
+                         "fp64": fp64},
+        })
     res["shader_clock_mhz"] = last.get("shader_clock_mhz", 0.0)
-    if a.inprocess and multi:
+    if a.full and a.inprocess and multi:
         # both ways of summing the devices' partials, timed in this run on this workload
         res["combine_ab"] = combine_ab(r, a, devices, max(3, min(a.steps, 10)))
         try:
@@ -822,16 +838,17 @@ def main():
             res["sustained"] = sustained(r, max(300, a.sustained_steps))
     if a.dump_outputs:
         res["dump_outputs"] = dumped
-    res["evaluations_in_this_run"] = r.n_eval   # of the headline workload (settle + warm-up + timed + profiled + callbacks)
-    if multi or devices is not None or ar_ms is not None:
+    res["evaluations_in_this_run"] = r.n_eval   # of the headline workload (settle + warm-up + timed [+ --full's passes])
+    rccl_dist = tdist is not None and backend == "nccl"
+    if multi or devices is not None or rccl_dist:
         res["combine"] = {"ms_allreduce": ar_ms, "ms_combine_inprocess": combine_ms if a.inprocess else None,
                           "mode": ["host", "host", "rccl"][last["combine"]] if a.inprocess else "torch.distributed",
-                          "rccl_ranks": (r.ctx.group_info()["rccl_ranks"] if a.inprocess else (world if ar_ms is not None else 0)),
-                          "note": "ms_allreduce: RCCL all-reduce of 19N+1 doubles alone (launch + sync, torchrun path); "
+                          "rccl_ranks": (r.ctx.group_info()["rccl_ranks"] if a.inprocess else (world if rccl_dist else 0)),
+                          "note": "ms_allreduce: RCCL all-reduce of 19N+1 doubles alone (launch + sync, torchrun path, --full); "
                                   "ms_combine_inprocess: host time from 'all devices done' to 'summed partial on the host'"}
     # release the headline workload before the sub-runs
     r.opt._ctx.close()
-    if multi and not a.no_extras:
+    if a.full and multi and not a.no_extras:
         # strong-scaling base measured in the same run: the same total cloud on ONE GPU (rank 0's / the first device),
         # so that the speed-up of this line does not have to be inferred from the N = 1 line of another workload
         import svsdf_amd
@@ -850,10 +867,10 @@ def main():
         res["strong_scaling_base"] = {"n_gpus": 1, "points_total": P_total, "steps": nb, "ms_per_step": base_ms,
                                       "value": P_total / (base_ms * 1e-3), "speedup_of_this_line": base_ms / ms_per_step,
                                       "note": "same workload, whole cloud resident on one GPU, measured by rank 0 after the timed region"}
-    if not multi and not a.no_extras and a.config is None and a.points is None and a.dist == "corridor":
+    if a.full and not multi and not a.no_extras and a.config is None and a.points is None and a.dist == "corridor":
         res["north_star"] = sub_run(a, "NS", workload.CONFIGS["NS"]["P"], "corridor", rank, world, local_rank, None, None, a.extra_steps)
         res["map_distribution"] = sub_run(a, name, P_total, "map", rank, world, local_rank, None, None, a.extra_steps)
-    if not multi and not a.no_extras and a.config is None and a.points is None and a.dist == "corridor":
+    if a.full and not multi and not a.no_extras and a.config is None and a.points is None and a.dist == "corridor":
         # every other BASELINE config at its full size on this GPU (compact objects), C4's whole 4 M cloud on ONE device
         # (the base of the N > 1 lines, which run C4), and what one optimisation pays from a cold context
         res["other_configs"] = {c: quick_run(c, workload.CONFIGS[c]["P"], st_, local_rank, generic=True)
@@ -861,7 +878,7 @@ def main():
         res["c4_one_gpu"] = quick_run("C4", workload.CONFIGS["C4"]["P"], 5, local_rank)
         res["first_optimisation"] = first_optimisation(name, P_total, local_rank)
         res["reference_scale"] = reference_scale(local_rank)
-    if not multi and not a.no_cpu_baseline:
+    if a.full and not multi and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(w, a.cpu_seconds)
         res["speedup_vs_cpu_baseline"] = value / res["cpu_baseline"]["value"]
         if "north_star" in res:

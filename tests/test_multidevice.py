@@ -193,7 +193,7 @@ def test_bench_c4_inprocess_two_stripes(built):
     only one GPU is visible): BASELINE configs[3], 4 M points in total, strong scaling."""
     import torch
     dev = "0,1" if torch.cuda.device_count() >= 2 else "0,0"
-    r = _bench(["--gpus", "2", "--config", "C4", "--inprocess", "--devices", dev, "--steps", "2", "--warmup", "1"])
+    r = _bench(["--gpus", "2", "--config", "C4", "--inprocess", "--devices", dev, "--steps", "2", "--warmup", "1", "--full"])
     assert r["n_gpus"] == 2 and r["config"]["points_total"] == 4000000 and r["scaling"] == "strong"
     assert r["config"]["points_per_gpu"] == 2000000 and r["value"] > 0
     assert r["combine"]["ms_combine_inprocess"] is not None and r["combine"]["ms_combine_inprocess"] < 1.0
@@ -207,13 +207,14 @@ def test_bench_gpus_n_drives_n_devices_by_itself(built):
     GPU and print n_gpus = 1."""
     import torch
     if torch.cuda.device_count() >= 2:
-        r = _bench(["--gpus", "2", "--points", "400000", "--steps", "2", "--warmup", "1", "--no-extras"])
+        r = _bench(["--gpus", "2", "--points", "400000", "--steps", "2", "--warmup", "1", "--full", "--no-extras"])
     else:
         e = dict(os.environ)
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"], env=e,
                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
         assert out.returncode != 0 and b"GPU(s) visible" in out.stderr, out.stderr.decode()[-500:]
-        r = _bench(["--gpus", "2", "--devices", "0,0", "--points", "400000", "--steps", "2", "--warmup", "1", "--no-extras"])
+        r = _bench(["--gpus", "2", "--devices", "0,0", "--points", "400000", "--steps", "2", "--warmup", "1", "--full",
+                    "--no-extras"])
     assert r["n_gpus"] == 2 and r["config"]["points_per_gpu"] == 200000 and r["scaling"] == "strong"
     assert r["config"]["shape"] == "sdHeart" and r["combine"]["ms_combine_inprocess"] is not None
     # both combines are timed in the same run (VERDICT r3 #4); the RCCL communicator must hold one rank per GPU -- read
@@ -245,7 +246,8 @@ def test_bench_c4_two_ranks_emulated(built):
     env = {} if torch.cuda.device_count() >= 2 else {"SVSDF_BENCH_ONE_GPU": "1", "SVSDF_BENCH_BACKEND": "gloo"}
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", str(port)]
-    r = _bench(["--gpus", "2", "--config", "C4", "--points", "400000", "--steps", "2", "--warmup", "1"], env, launcher)
+    r = _bench(["--gpus", "2", "--config", "C4", "--points", "400000", "--steps", "2", "--warmup", "1", "--full"], env,
+               launcher)
     assert r["n_gpus"] == 2 and r["config"]["points_total"] == 400000 and r["config"]["points_per_gpu"] == 200000
     assert r["scaling"] == "strong" and r["value"] > 0
     assert r["strong_scaling_base"]["speedup_of_this_line"] > 0

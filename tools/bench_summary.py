@@ -1,4 +1,4 @@
-"""Print the numbers of a default bench line (and optionally a stripes line) one per row: python tools/bench_summary.py <bench.json> [<stripes.json>]"""
+"""Print the numbers of a bench.py --full line (and optionally a stripes line) one per row: python tools/bench_summary.py <bench.json> [<stripes.json>]"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print('C3 ms', round(d['ms_per_step'], 3), 'Mpts/s', round(d['value'] / 1e6, 1), 'generic', round(d['generic_durations']['ms_per_step'], 3), 'sustained', round(d['sustained']['ms_per_step'], 3),

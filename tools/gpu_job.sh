@@ -6,11 +6,11 @@
 #   refscale     bench.py --only reference_scale
 #   reftrace     rocprofv3 kernel trace + per-launch timeline of a reference-scale callback (star map)
 #   site:<lib>[:<configs>]   tools/site_stats.py of a -DSVSDF_SITE_STATS variant build (default C3,NS; ref:star = reference scale)
-#   bench        bench.py default line (N = 1)
-#   benchq       bench.py --no-extras --no-cpu-baseline (headline only)
+#   bench        bench.py --full line (N = 1)
+#   benchq       bench.py --full --no-extras --no-cpu-baseline (headline, roofline, callbacks, generic durations)
 #   benchv:<variant>   the same with libsvsdf_hip_<variant>.so (SVSDF_LIB_VARIANT)
 #   abenv:<spec>[:<configs>[:<points>]]   tools/ab_env.py on the default library ("A=1;B=2": first spec = baseline)
-#   stripes8     bench.py --gpus 8 --devices 0,0,0,0,0,0,0,0 --config C4 (8 stripes on this GPU)
+#   stripes8     bench.py --full --gpus 8 --devices 0,0,0,0,0,0,0,0 --config C4 (8 stripes on this GPU)
 #   ab:<variants>[:<configs>[:<points>]]   tools/exp_variants.py (variant builds vs the default library, identity hash)
 #   pytest[:<expr>]   pytest -m gpu [-k expr]
 #   fuzz:<cases>:<seed>   tools/fuzz_parity.py campaign
@@ -40,16 +40,16 @@ for STEP in "$@"; do
        [ -n "$KS" ] && cp $KS $OUT/${TAG}_reftrace_kernel_stats.csv
        [ -n "$KT" ] && python $ROOT/tools/timeline.py $KT 9 > $OUT/${TAG}_reftrace_timeline.txt 2>&1) ;;
     site)     IFS=: read -r V C <<< "$ARG"; timeout 400 python -u tools/site_stats.py ${V:-st} ${C:-C3,NS} > $OUT/${TAG}_site_${V:-st}.txt 2>&1 ;;
-    bench)    timeout 900 python -u bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err ;;
-    benchq)   timeout 300 python -u bench.py --no-extras --no-cpu-baseline > $OUT/${TAG}_bench_quick.json 2> $OUT/${TAG}_bench_quick.err ;;
-    benchv)   SVSDF_LIB_VARIANT=$ARG timeout 300 python -u bench.py --no-extras --no-cpu-baseline > $OUT/${TAG}_bench_quick_$ARG.json 2> $OUT/${TAG}_bench_quick_$ARG.err ;;
+    bench)    timeout 900 python -u bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err ;;
+    benchq)   timeout 300 python -u bench.py --full --no-extras --no-cpu-baseline > $OUT/${TAG}_bench_quick.json 2> $OUT/${TAG}_bench_quick.err ;;
+    benchv)   SVSDF_LIB_VARIANT=$ARG timeout 300 python -u bench.py --full --no-extras --no-cpu-baseline > $OUT/${TAG}_bench_quick_$ARG.json 2> $OUT/${TAG}_bench_quick_$ARG.err ;;
     abenv)    IFS=: read -r SPEC C P <<< "$ARG"; timeout 600 python -u tools/ab_env.py - "$SPEC" ${C:-C3,NS} ${P:-0} > $OUT/${TAG}_abenv_$(echo ${C:-C3,NS} | tr ',' '_')_${P:-0}.txt 2>&1 ;;
-    stripes8) timeout 600 python -u bench.py --gpus 8 --devices 0,0,0,0,0,0,0,0 --config C4 --steps 10 --no-extras > $OUT/${TAG}_stripes8.json 2> $OUT/${TAG}_stripes8.err ;;
+    stripes8) timeout 600 python -u bench.py --full --gpus 8 --devices 0,0,0,0,0,0,0,0 --config C4 --steps 10 --no-extras > $OUT/${TAG}_stripes8.json 2> $OUT/${TAG}_stripes8.err ;;
     ab)       IFS=: read -r V C P <<< "$ARG"; timeout 900 python -u tools/exp_variants.py "$V" ${C:-C3,NS} ${P:-1000000} > $OUT/${TAG}_ab_$(echo $V | tr ',' '_')_$(echo ${C:-C3,NS} | tr ',' '_').txt 2>&1 ;;
     pytest)   if [ -n "$ARG" ]; then timeout 1500 python -m pytest tests -x -q -m gpu -k "$ARG" > $OUT/${TAG}_pytest.txt 2>&1; else timeout 1500 python -m pytest tests -x -q -m gpu --durations=20 > $OUT/${TAG}_pytest.txt 2>&1; fi; tail -3 $OUT/${TAG}_pytest.txt ;;
     fuzz)     IFS=: read -r N S <<< "$ARG"; timeout 900 python -u tools/fuzz_parity.py ${N:-100} ${S:-1} > $OUT/${TAG}_fuzz_${S:-1}.txt 2>&1 ;;
     kt)
-      (cd /tmp && rm -rf /tmp/kt_$TAG && SVSDF_BATCHES=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$TAG -o kt -- python -u $ROOT/bench.py --config $ARG --steps 5 --warmup 1 --no-cpu-baseline --no-extras > $OUT/${TAG}_kt_$ARG.log 2>&1
+      (cd /tmp && rm -rf /tmp/kt_$TAG && SVSDF_BATCHES=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$TAG -o kt -- python -u $ROOT/bench.py --config $ARG --steps 5 --warmup 1 --full --no-cpu-baseline --no-extras > $OUT/${TAG}_kt_$ARG.log 2>&1
        KS=$(find /tmp/kt_$TAG -name '*kernel_stats.csv' | head -1); KT=$(find /tmp/kt_$TAG -name '*kernel_trace.csv' | head -1)
        [ -n "$KS" ] && cp $KS $OUT/${TAG}_bench_${ARG}_b1_kernel_stats.csv
        [ -n "$KT" ] && python $ROOT/tools/timeline.py $KT 6 > $OUT/${TAG}_bench_${ARG}_b1_timeline.txt 2>&1) ;;

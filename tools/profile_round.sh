@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python -u $ROOT/bench.py --config $CFG --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+BENCH="python -u $ROOT/bench.py --config $CFG --steps 5 --warmup 1 --full --no-cpu-baseline --no-extras"
 timeout 600 $BENCH > $OUT/${TAG}_bench_${CFG}_short.json 2> $OUT/${TAG}_bench.err
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_kt -o kt -- $BENCH > $OUT/${TAG}_kt.log 2>&1
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/${TAG}_pmc_f -o f -- $BENCH > $OUT/${TAG}_pmc_f.log 2>&1
@@ -22,7 +22,7 @@ S=$(find $OUT/${TAG}_pmc_s -name '*counter_collection.csv' | head -1)
 # evaluations per profiled run: bench.py counts them itself (settle + warm-up + timed + event-profiled + serialised-profiled +
 # generic-durations + full-callback passes)
 NEV=$(python -c "import json,sys; print(json.load(open('$OUT/${TAG}_bench_${CFG}_short.json'))['evaluations_in_this_run'])")
-python $ROOT/tools/pmc_summary.py $F $W $S ${3:-$NEV} "rocprofv3 PMC summary, bench.py --config $CFG --steps 5 --warmup 1 --no-cpu-baseline --no-extras, 1x MI355X, $TAG" > $OUT/${TAG}_bench_${CFG}_pmc_summary.txt
+python $ROOT/tools/pmc_summary.py $F $W $S ${3:-$NEV} "rocprofv3 PMC summary, bench.py --config $CFG --steps 5 --warmup 1 --full --no-cpu-baseline --no-extras, 1x MI355X, $TAG" > $OUT/${TAG}_bench_${CFG}_pmc_summary.txt
 KT=$(find $OUT/${TAG}_kt -name '*kernel_trace.csv' | head -1)
 python $ROOT/tools/timeline.py $KT 6 > $OUT/${TAG}_bench_${CFG}_timeline.txt 2>&1
 rm -rf $OUT/${TAG}_kt $OUT/${TAG}_pmc_f $OUT/${TAG}_pmc_w $OUT/${TAG}_pmc_s
