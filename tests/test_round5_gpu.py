@@ -101,6 +101,16 @@ def test_reference_scale_callback(built, name, monkeypatch):
         c.close()
     f, g, _ = got["default"]
     assert abs(f - fo) <= 1e-7 * abs(fo) and _rel(g, go) <= 1e-5, (f, fo, _rel(g, go))
+    # per point, bit for bit, on the trajectory the device stage received (host MINCO and the oracle's may differ in the
+    # last bits, so the callback itself is held to the gates above): device-library trig, the reference's chain
+    od = orc.Oracle(name, **kw)
+    od.set_traj(coeffs, T)
+    od.set_modes(1, 0)
+    osdf, ots, og = od.query(w["points"], nthreads=NT)
+    sdf, ts, gp = got["default"][2]
+    nbad = int(((sdf != osdf) | (ts != ots) | (gp != og).any(axis=1)).sum())
+    print(f"{name}: N {len(T)} total {T.sum():.3f} s, {len(sdf)} points, {nbad} per-point mismatches")
+    assert nbad == 0, (name, int((sdf != osdf).sum()), int((ts != ots).sum()))
     for label in ("tail, global state", "chain"):
         assert got[label][0] == f and np.array_equal(got[label][1], g), label
         for a, b in zip(got[label][2], got["default"][2]):
@@ -248,6 +258,19 @@ def test_more_than_64_pieces(built, N, piece_s):
     assert np.abs(sdf[~flips] - osdf[~flips]).max() <= 1e-7
     assert abs(cost - ocost) <= 1e-7 * abs(ocost), (cost, ocost)
     assert _rel(gC, ogC) <= 1e-5 and _rel(gT, ogT) <= 1e-5, (_rel(gC, ogC), _rel(gT, ogT))
+    # device arithmetic (the device library's trig, the reference's chain of subtractions): every per-point value bit for
+    # bit, the sums to summation order
+    od = _oracle(w)
+    od.set_traj(w["coeffs"], w["T"])
+    od.set_modes(1, 0)
+    dcost, dgT, dgC, dsdf, dts, _ = od.penalty(w["points"], nthreads=NT, sum_mode=1, per_point=True)
+    dg = od.query(w["points"], nthreads=NT)[2]
+    nbad = int(((sdf != dsdf) | (ts != dts) | (g != dg).any(axis=1)).sum())
+    print(f"N {N}: total {w['T'].sum():.3f} s mode {c.stats()['piece_time_exact']}, {nbad} per-point mismatches of {len(sdf)}")
+    assert c.stats()["piece_time_exact"] == 1
+    assert nbad == 0, (N, int((sdf != dsdf).sum()), int((ts != dts).sum()))
+    assert abs(cost - dcost) <= 1e-12 * abs(dcost), (cost, dcost)
+    assert _rel(gC, dgC) <= 1e-12 and _rel(gT, dgT) <= 1e-12, (_rel(gC, dgC), _rel(gT, dgT))
     x = workload.x_from(w["q"], w["T"], svsdf_amd.backward_T)
     f, gx = c.lmbm_evaluate(x)
     fo, go, c3 = o.cost_function(w["points"], x, nthreads=NT)
