@@ -516,8 +516,9 @@ int svsdf_get_plan(const svsdf_ctx *ctx, svsdf_plan *out) {
   const svsdf_ctx *c = ctx->subs.empty() ? ctx : ctx->subs[0];
   out->bound_mode = bound_mode_of(c);
   out->batches = (c->saved_nbatch > 0) ? c->saved_nbatch : c->nbatch;
-  out->lanes_per_query = c->G;
-  out->tail_iter = (c->tail_mode == -2) ? -2 : (c->tail_mode >= 0) ? c->tail_mode : (c->have_prev_nactive ? choose_tail_iter(c) : SVSDF_PLAN_AUTO);
+  // (the scaled path: widths 4 / 8 / 32 and no fused tail, §4c; a width not chosen yet stays 0 = by shard size, as on the rigid path)
+  out->lanes_per_query = (c->scaled && c->G > 0) ? svsdf::scaled_lanes(c->G) : c->G;
+  out->tail_iter = (c->tail_mode == -2 || c->scaled) ? -2 : (c->tail_mode >= 0) ? c->tail_mode : (c->have_prev_nactive ? choose_tail_iter(c) : SVSDF_PLAN_AUTO);
   out->settled = ((c->ub_env || c->ub_tune > 0) && c->bt_state == 0 && c->an_state == 0 && c->lz_state == 0 && c->have_prev_nsolve) ? 1 : 0;
   return SVSDF_OK;
 }
@@ -558,6 +559,46 @@ int svsdf_set_plan(svsdf_ctx *ctx, const svsdf_plan *plan) {
     if (!ctx->G_late_env) ctx->G_late = std::max(ctx->G, 8);
   }
   ctx->tail_mode = (plan->tail_iter == SVSDF_PLAN_AUTO) ? -1 : plan->tail_iter;
+  return SVSDF_OK;
+}
+
+// Time-varying robot scale.  Validated once here; a group context hands it to every stripe.
+int svsdf_set_scale(svsdf_ctx *ctx, const svsdf_scale *scale) {
+  if (!ctx) return SVSDF_ERR_INVALID;
+  svsdf::ScaleDev d{};
+  bool on = false;
+  if (scale) {
+    if (scale->struct_size != (int)sizeof(svsdf_scale))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_set_scale: struct_size is not sizeof(svsdf_scale)");
+    on = scale->enabled != 0;
+    if (on) {
+      for (int a = 0; a < 2; ++a) {
+        const double v[4] = {scale->c[a], scale->amp[a], scale->omega[a], scale->phase[a]};
+        for (double x : v)
+          if (!std::isfinite(x)) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_set_scale: non-finite parameter");
+        if (!(scale->c[a] - std::fabs(scale->amp[a]) > 0.0))
+          return fail(ctx, SVSDF_ERR_INVALID, std::string("svsdf_set_scale: s_") + (a ? "y" : "x") +
+                                                  "(t) can reach 0 (c - |A| <= 0): S(t) would be singular");
+      }
+      d = svsdf::ScaleDev{scale->c[0], scale->amp[0], scale->omega[0], scale->phase[0],
+                          scale->c[1], scale->amp[1], scale->omega[1], scale->phase[1]};
+    }
+  }
+  // (the swept outline's cached result belongs to the old schedule)
+  for (svsdf_ctx *s : ctx->subs) { s->scaled = on; s->scale = d; s->ol_valid = false; }
+  ctx->scaled = on;
+  ctx->scale = d;
+  ctx->ol_valid = false;
+  return SVSDF_OK;
+}
+
+int svsdf_get_scale(const svsdf_ctx *ctx, svsdf_scale *out) {
+  if (!ctx || !out) return SVSDF_ERR_INVALID;
+  if (out->struct_size != (int)sizeof(svsdf_scale)) return SVSDF_ERR_INVALID;
+  const svsdf::ScaleDev &d = ctx->scale;
+  out->enabled = ctx->scaled ? 1 : 0;
+  out->c[0] = ctx->scaled ? d.cx : 1.0; out->amp[0] = d.ax; out->omega[0] = d.wx; out->phase[0] = d.phx;
+  out->c[1] = ctx->scaled ? d.cy : 1.0; out->amp[1] = d.ay; out->omega[1] = d.wy; out->phase[1] = d.phy;
   return SVSDF_OK;
 }
 

@@ -165,6 +165,10 @@ struct svsdf_ctx {
   double scan_delta = 0.002;   // the same band in the scanning bound modes, where the bound is the sample's own table minimum (round 6 sweep, 0 ... 0.01:
                                // sdHeart / anchor mode - 3.5 % at 0.001 - 0.002 m -- 7 % fewer solves --, C3 / NS / C5 / C2 within +- 0.5 %; 0.01 m until round 5)
   double select_delta = 0.1;  // k_round: solve the samples whose upper bound is within this of the best one first
+  // time-varying robot scale (svsdf_set_scale): the scaled kernels, launch chain only, no culls, every GSIP
+  // sample requested
+  bool scaled = false;
+  svsdf::ScaleDev scale{};
 
   // per-point / per-sub-query buffers
   double *d_sdf = nullptr, *d_t = nullptr;

@@ -304,6 +304,8 @@ int svsdf_swept_outline(svsdf_ctx *ctx, int N, const double *coeffs, const doubl
   c.polygon_nloops = (int)base->poly_loops.size();
   svsdf_ctx *tmp = svsdf_create(&c);
   if (!tmp) return fail(ctx, SVSDF_ERR_INVALID, std::string("svsdf_swept_outline: ") + svsdf_last_error_string(nullptr));
+  tmp->scaled = ctx->scaled;   // sw_calculate runs <useScale> too: the caller's scale schedule (svsdf_set_scale)
+  tmp->scale = ctx->scale;
   std::vector<double> xyz, sdf;
   std::vector<long long> idx;
   const svsdf_host::FieldEval eval = [&](const std::vector<double> &xy, std::vector<double> &val) -> int {

@@ -105,4 +105,24 @@ k_debug_sdf_at(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__
   o[1] = p.x; o[2] = p.y; o[3] = p.cs; o[4] = p.sn; o[5] = rx; o[6] = ry; o[7] = (double)tr.exact;
 }
 
+// the same under a time-varying scale (§4c): getSDFAtTimeStamp<true>, out8[5..6] = the scaled body-frame point u
+template <int SHAPE>
+__global__ void __launch_bounds__(64)
+k_debug_sdf_at_sc(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__restrict__ pxy, const double *__restrict__ t_,
+                  int n, double *__restrict__ out, ScaleDev scl) {
+  extern __shared__ double dbg_lds[];
+  const TrajL tr = stage_traj(trg, dbg_lds);
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  PieceCache pc = piece_cache_init();
+  const Pose p = pose_at(tr, t_[i], pc);
+  const double px = pxy[2 * i], py = pxy[2 * i + 1];
+  double i00, i11, rx, ry;
+  scale_inv(scl, t_[i], i00, i11);
+  rel_scaled(p, px, py, i00, i11, rx, ry);
+  double *o = out + 8 * (size_t)i;
+  o[0] = shape_sdf<SHAPE>(sp, rx, ry);
+  o[1] = p.x; o[2] = p.y; o[3] = p.cs; o[4] = p.sn; o[5] = rx; o[6] = ry; o[7] = (double)tr.exact;
+}
+
 }  // namespace svsdf

@@ -17,6 +17,7 @@ struct SolveLaunch {   // arguments of k_solve<SHAPE, G, 1>
   const TrajDev *traj; const double *tk; const Pose *pose; const Chunk *chunks; ShapeParams sp; QuerySet qs;
   double *out_sdf, *out_t; int prune; BatchCtl *ctl; int work_idx; double cull_thresh;
   const double *rot; double slack_max;   // second exact cull (main points): per-chunk yaw allowance W_c h, max_c of the linear one
+  const ScaleDev *scl = nullptr;         // not null: k_solve_sc<SHAPE, G, 1> under this scale schedule (G in kScaledLanes)
 };
 struct RoundLaunch {   // arguments of k_round<SHAPE, LP, MODE>
   const TrajDev *traj; const Pose *pose; const Chunk *chunks; ShapeParams sp; const double *px, *py; GsipState gs;
@@ -32,7 +33,11 @@ struct TailLaunch {    // arguments of k_tail<SHAPE, MODE, WAVES>
 struct ClassifyLaunch {   // arguments of k_classify<SHAPE>
   const TrajDev *traj; ShapeParams sp; const double *px, *py, *sdf, *t; double *res_sdf, *res_t, *res_gx, *res_gy;
   GsipState gs; BatchCtl *ctl; int *n_int; int icap;
+  const ScaleDev *scl = nullptr;   // not null: k_classify_sc<SHAPE>
 };
+// lane-group widths the scaled solve is instantiated for (§4c: a reduced plan space); scaled_lanes maps any width onto them
+constexpr int kScaledLanes[3] = {4, 8, 32};
+inline int scaled_lanes(int G) { return G >= 32 ? 32 : G >= 8 ? 8 : 4; }
 
 // each returns false when the shape id is not compiled into the library (development builds)
 bool launch_k_solve(int shape, int G, unsigned grid, unsigned block, size_t lds, hipStream_t st, const SolveLaunch &a);
@@ -45,7 +50,7 @@ bool launch_k_subsw(int shape, dim3 grid, hipStream_t st, ShapeParams sp, const 
 bool launch_k_shape_kernels(int shape, unsigned grid, hipStream_t st, ShapeParams sp, int ks, int count, double resu,
                             int size_side, double safemargin, const double *yaw, unsigned char *map);
 bool launch_k_debug_sdf_at(int shape, unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp,
-                           const double *pxy, const double *t, int n, double *out);
+                           const double *pxy, const double *t, int n, double *out, const ScaleDev *scl = nullptr);
 
 // per-slice entry points (defined by svsdf_shape_slice.hip, one set per slice)
 #define SVSDF_DECLARE_SLICE(K)                                                                                              \
@@ -59,7 +64,7 @@ bool launch_k_debug_sdf_at(int shape, unsigned grid, size_t lds, hipStream_t st,
   bool launch_k_shape_kernels_s##K(int shape, unsigned grid, hipStream_t st, ShapeParams sp, int ks, int count, double resu,   \
                                    int size_side, double safemargin, const double *yaw, unsigned char *map);                   \
   bool launch_k_debug_sdf_at_s##K(int shape, unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp,    \
-                                  const double *pxy, const double *t, int n, double *out);
+                                  const double *pxy, const double *t, int n, double *out, const ScaleDev *scl);
 SVSDF_DECLARE_SLICE(0)
 SVSDF_DECLARE_SLICE(1)
 SVSDF_DECLARE_SLICE(2)

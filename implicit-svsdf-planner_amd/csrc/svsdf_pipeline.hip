@@ -151,9 +151,9 @@ bool launch_k_subsw(int shape, dim3 grid, hipStream_t st, ShapeParams sp, const 
   SVSDF_SLICE_DISPATCH(launch_k_subsw, grid, st, sp, father, child, offs, pts, kt, nkt, flag)
 }
 bool launch_k_debug_sdf_at(int shape, unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp,
-                           const double *pxy, const double *t, int n, double *out) {
+                           const double *pxy, const double *t, int n, double *out, const ScaleDev *scl) {
   shape = svsdf_impl::compiled_shape(shape);
-  SVSDF_SLICE_DISPATCH(launch_k_debug_sdf_at, grid, lds, st, traj, sp, pxy, t, n, out)
+  SVSDF_SLICE_DISPATCH(launch_k_debug_sdf_at, grid, lds, st, traj, sp, pxy, t, n, out, scl)
 }
 bool launch_k_shape_kernels(int shape, unsigned grid, hipStream_t st, ShapeParams sp, int ks, int count, double resu,
                             int size_side, double safemargin, const double *yaw, unsigned char *map) {
@@ -173,6 +173,11 @@ void launch_solve(svsdf_ctx *ctx, int G, hipStream_t st, const QuerySet &qs, lon
                   double *out_t, BatchCtl *ctl, int work_idx,
                   double cull_thresh = std::numeric_limits<double>::infinity()) {
   const double *d_tk = ctx->d_in + 19 * (size_t)ctx->N;
+  if (ctx->scaled) {
+    // the scaled path (§4c): its widths only, and no cull -- both culls bound the rigid map, not the scaled descent's value
+    G = scaled_lanes(G);
+    cull_thresh = std::numeric_limits<double>::infinity();
+  }
   // a launch of at most one query per SIMD with 32-lane groups (the main solve of a reference-scale cloud): one query per
   // wave, so that the descents take the fused pass (k_solve, `prune` bit 1)
   const bool solo = G == 32 && !ctx->G_env && max_queries <= (long long)ctx->n_cu * 4;
@@ -205,11 +210,11 @@ void launch_solve(svsdf_ctx *ctx, int G, hipStream_t st, const QuerySet &qs, lon
   const bool cull2 = std::isfinite(cull_thresh) && ctx->cull2;
   const double *d_rot = d_tk + ctx->K + (ctx->K + kChunk - 1) / kChunk;
   const SolveLaunch a{ctx->d_traj, d_tk, ctx->d_pose, ctx->d_chunks, ctx->sp, qs, out_sdf, out_t, ctx->prune | (solo ? 2 : 0), ctl, work_idx, cull_thresh,
-                      cull2 ? d_rot : nullptr, ctx->slack_max};
+                      cull2 ? d_rot : nullptr, ctx->slack_max, ctx->scaled ? &ctx->scale : nullptr};
   const int shape = poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
   if (!launch_k_solve(shape, G, grid, (unsigned)blk, lds_total, st, a) && ctx->launch_err.empty())
     ctx->launch_err = "k_solve: shape not compiled into this build";
-  if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_SOLVE, compiled_shape(shape), grid, (unsigned)blk, lds_total, max_queries,
+  if (svsdf_launch_rec *r = record_launch(ctx, ctx->scaled ? SVSDF_KERNEL_SOLVE_SCALED : SVSDF_KERNEL_SOLVE, compiled_shape(shape), grid, (unsigned)blk, lds_total, max_queries,
                                           (int)(ctl - ctx->d_ctl))) {
     r->targ[0] = G; r->targ[1] = 1; r->iter = work_idx; r->solo = solo ? 1 : 0;
   }
@@ -242,8 +247,10 @@ void launch_round(svsdf_ctx *ctx, hipStream_t st, int b, int it) {
   // iteration 7); the chunk bound of the cheap mode needs 0.1 m / iteration 5.  SVSDF_SELECT_DELTA overrides both.
   const double sel = (scans && !ctx->select_env) ? ctx->scan_delta : ctx->select_delta;
   const int all_it = (scans && !ctx->all_iter_env) ? 7 : ctx->delta_all_iter;
-  const double delta = (it >= all_it) ? 1e300 : sel;
-  const double band_delta = (it >= all_it) ? 1e300 : ctx->select_delta;   // lazy mode: cheap-bound band that gets scanned
+  // the scaled path (§4c) requests every sample in every iteration: the bounds are values of the RIGID table, and a scaled
+  // solve from a rigid seed is bounded by none of them
+  const double delta = (it >= all_it || ctx->scaled) ? 1e300 : sel;
+  const double band_delta = (it >= all_it || ctx->scaled) ? 1e300 : ctx->select_delta;   // lazy mode: cheap-bound band that gets scanned
   // iterations 0 and 1 are (almost always) GSIP rounds 1 and 2 with 2 and 6 samples: 8 lanes per point; later rounds have
   // 18-21 samples: 32 lanes per point (either handles any count).  Iteration 2 (18 samples, still every interior point
   // active: throughput, not latency) also runs faster with 8 lanes and three sample passes per point -- measured round 3,
@@ -342,7 +349,7 @@ void launch_tail(svsdf_ctx *ctx, hipStream_t st, int b, int it0) {
 // 1.06, 30 k (14 k) 1.24 -> 1.56 (tools/tail_scan.py).  SVSDF_TAIL / svsdf_set_plan pin an iteration or turn the tail
 // off.  Any choice gives the same bits.
 int choose_tail_iter(const svsdf_ctx *ctx) {
-  if (ctx->tail_mode == -2) return -1;
+  if (ctx->tail_mode == -2 || ctx->scaled) return -1;   // (the scaled path runs the launch chain only, §4c)
   //  a trajectory whose tables leave no room for the tail's per-wave state runs the launch chain, which needs
   // less LDS per block, instead of failing the evaluation (128 pieces on a device with 64 KB per block)
   if (tail_lds_bytes(ctx, false, false) > ctx->lds_limit) return -1;
@@ -356,9 +363,12 @@ void launch_classify(svsdf_ctx *ctx, hipStream_t st, int b) {
   const unsigned grid = (unsigned)std::min<long long>(((long long)ctx->bcount[b] + kBlock - 1) / kBlock, 2048);
   const size_t lds = (size_t)traj_lds_doubles(ctx->N) * sizeof(double);
   const ClassifyLaunch a{ctx->d_traj, ctx->sp, ctx->d_px, ctx->d_py, ctx->d_sdf, ctx->d_t, ctx->d_res_sdf, ctx->d_res_t,
-                         ctx->d_res_gx, ctx->d_res_gy, ctx->gs, ctx->d_ctl + b, &ctx->d_ctl->n_int, (int)ctx->icap};
-  (void)launch_k_classify(ctx->cfg.shape_id, grid, lds, st, a);
-  (void)record_launch(ctx, SVSDF_KERNEL_CLASSIFY, compiled_shape(ctx->cfg.shape_id), grid, (unsigned)kBlock, lds, ctx->bcount[b], b);
+                         ctx->d_res_gx, ctx->d_res_gy, ctx->gs, ctx->d_ctl + b, &ctx->d_ctl->n_int, (int)ctx->icap,
+                         ctx->scaled ? &ctx->scale : nullptr};
+  if (!launch_k_classify(ctx->cfg.shape_id, grid, lds, st, a) && ctx->launch_err.empty())
+    ctx->launch_err = "k_classify: shape not compiled into this build";
+  (void)record_launch(ctx, ctx->scaled ? SVSDF_KERNEL_CLASSIFY_SCALED : SVSDF_KERNEL_CLASSIFY, compiled_shape(ctx->cfg.shape_id), grid,
+                      (unsigned)kBlock, lds, ctx->bcount[b], b);
   debug_sync(st, "k_classify", b, 0);
 }
 
@@ -641,11 +651,19 @@ int reduce_and_read(svsdf_ctx *ctx, bool with_partial) {
     // launch whose last block writes the result to the device buffer and straight into the pinned host buffer (k_reduce);
     // larger ones: the assembly, then k_final (one wave per entry) and k_finish as launches of their own
     const int fuse = grid <= 4 ? 1 : 0;
-    hipLaunchKernelGGL(k_reduce, dim3(grid), dim3(kBlock), lds, ctx->stream, ctx->d_traj, ctx->d_px, ctx->d_py,
-                       (int)ctx->P, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
-                       ctx->cfg.safety_hor, ctx->cfg.weight_p, ctx->d_block_partials, ctx->d_nonfinite, ctx->d_out,
-                       ctx->d_ctl, ctx->nbatch, ctx->it_done, (int)kOutPartial, (int)kOutDoubles, ctx->d_ticket, ctx->h_out_dev, fuse);
-    if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_REDUCE, -1, grid, (unsigned)kBlock, lds, (long long)ctx->P, 0)) r->fused = fuse;
+    if (ctx->scaled)   // the position gradient under S(t*) (§4c)
+      hipLaunchKernelGGL(k_reduce_sc, dim3(grid), dim3(kBlock), lds, ctx->stream, ctx->d_traj, ctx->d_px, ctx->d_py,
+                         (int)ctx->P, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
+                         ctx->cfg.safety_hor, ctx->cfg.weight_p, ctx->d_block_partials, ctx->d_nonfinite, ctx->d_out,
+                         ctx->d_ctl, ctx->nbatch, ctx->it_done, (int)kOutPartial, (int)kOutDoubles, ctx->d_ticket, ctx->h_out_dev, fuse,
+                         ctx->scale);
+    else
+      hipLaunchKernelGGL(k_reduce, dim3(grid), dim3(kBlock), lds, ctx->stream, ctx->d_traj, ctx->d_px, ctx->d_py,
+                         (int)ctx->P, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
+                         ctx->cfg.safety_hor, ctx->cfg.weight_p, ctx->d_block_partials, ctx->d_nonfinite, ctx->d_out,
+                         ctx->d_ctl, ctx->nbatch, ctx->it_done, (int)kOutPartial, (int)kOutDoubles, ctx->d_ticket, ctx->h_out_dev, fuse);
+    if (svsdf_launch_rec *r = record_launch(ctx, ctx->scaled ? SVSDF_KERNEL_REDUCE_SCALED : SVSDF_KERNEL_REDUCE, -1, grid, (unsigned)kBlock, lds,
+                                            (long long)ctx->P, 0)) r->fused = fuse;
     if (!fuse) {
       hipLaunchKernelGGL(k_final, dim3((unsigned)plen), dim3(64), 0, ctx->stream, ctx->d_block_partials, (int)grid, ctx->d_sums);
       (void)record_launch(ctx, SVSDF_KERNEL_FINAL, -1, (unsigned)plen, 64, 0, (long long)grid, 0);
@@ -1249,7 +1267,8 @@ int debug_sdf_at(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, s
   if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
     const size_t lds = (size_t)traj_lds_doubles(N) * sizeof(double);
-    if (!launch_k_debug_sdf_at(ctx->cfg.shape_id, (unsigned)((n + 63) / 64), lds, ctx->stream, ctx->d_traj, ctx->sp, d_p, d_t, (int)n, d_o)) {
+    if (!launch_k_debug_sdf_at(ctx->cfg.shape_id, (unsigned)((n + 63) / 64), lds, ctx->stream, ctx->d_traj, ctx->sp, d_p, d_t, (int)n, d_o,
+                               ctx->scaled ? &ctx->scale : nullptr)) {
       cleanup();
       return fail(ctx, SVSDF_ERR_INVALID, "svsdf_debug_sdf_at: shape not compiled into this build");
     }

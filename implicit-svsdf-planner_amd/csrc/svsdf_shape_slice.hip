@@ -38,6 +38,19 @@ bool solve_s(int G, unsigned grid, unsigned block, size_t lds, hipStream_t st, c
   if constexpr (!kernel_shape_enabled<S>()) {
     return false;
   } else {
+    if (a.scl) {   // the scaled path (§4c): widths kScaledLanes only
+#define SOLVE_SC(GG)                                                                                                 \
+  hipLaunchKernelGGL((k_solve_sc<S, GG, 1>), dim3(grid), dim3(block), lds, st, a.traj, a.tk, a.pose, a.chunks, a.sp, \
+                     a.qs, a.out_sdf, a.out_t, a.prune, a.ctl, a.work_idx, a.cull_thresh, a.rot, a.slack_max, *a.scl)
+      switch (G) {
+        case 32: SOLVE_SC(32); break;
+        case 8: SOLVE_SC(8); break;
+        case 4: SOLVE_SC(4); break;
+        default: return false;
+      }
+#undef SOLVE_SC
+      return true;
+    }
 #define SOLVE(GG)                                                                                                   \
   hipLaunchKernelGGL((k_solve<S, GG, 1>), dim3(grid), dim3(block), lds, st, a.traj, a.tk, a.pose, a.chunks, a.sp,    \
                      a.qs, a.out_sdf, a.out_t, a.prune, a.ctl, a.work_idx, a.cull_thresh, a.rot, a.slack_max)
@@ -97,8 +110,12 @@ bool classify_s(unsigned grid, size_t lds, hipStream_t st, const ClassifyLaunch 
   if constexpr (!shape_enabled<S>()) {
     return false;
   } else {
-    hipLaunchKernelGGL((k_classify<S>), dim3(grid), dim3(kBlock), lds, st, a.traj, a.sp, a.px, a.py, a.sdf, a.t,
-                       a.res_sdf, a.res_t, a.res_gx, a.res_gy, a.gs, a.ctl, a.n_int, a.icap);
+    if (a.scl)
+      hipLaunchKernelGGL((k_classify_sc<S>), dim3(grid), dim3(kBlock), lds, st, a.traj, a.sp, a.px, a.py, a.sdf, a.t,
+                         a.res_sdf, a.res_t, a.res_gx, a.res_gy, a.gs, a.ctl, a.n_int, a.icap, *a.scl);
+    else
+      hipLaunchKernelGGL((k_classify<S>), dim3(grid), dim3(kBlock), lds, st, a.traj, a.sp, a.px, a.py, a.sdf, a.t,
+                         a.res_sdf, a.res_t, a.res_gx, a.res_gy, a.gs, a.ctl, a.n_int, a.icap);
     return true;
   }
 }
@@ -137,11 +154,12 @@ bool shape_kernels_s(unsigned grid, hipStream_t st, ShapeParams sp, int ks, int 
 
 template <int S>
 bool debug_sdf_at_s(unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp, const double *pxy,
-                    const double *t, int n, double *out) {
+                    const double *t, int n, double *out, const ScaleDev *scl) {
   if constexpr (!shape_enabled<S>()) {
     return false;
   } else {
-    hipLaunchKernelGGL((k_debug_sdf_at<S>), dim3(grid), dim3(64), lds, st, traj, sp, pxy, t, n, out);
+    if (scl) hipLaunchKernelGGL((k_debug_sdf_at_sc<S>), dim3(grid), dim3(64), lds, st, traj, sp, pxy, t, n, out, *scl);
+    else hipLaunchKernelGGL((k_debug_sdf_at<S>), dim3(grid), dim3(64), lds, st, traj, sp, pxy, t, n, out);
     return true;
   }
 }
@@ -190,8 +208,8 @@ bool SLICE_FN(launch_k_subsw)(int shape, dim3 grid, hipStream_t st, ShapeParams 
 #undef CALL
 }
 bool SLICE_FN(launch_k_debug_sdf_at)(int shape, unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp,
-                                     const double *pxy, const double *t, int n, double *out) {
-#define CALL(S) debug_sdf_at_s<S>(grid, lds, st, traj, sp, pxy, t, n, out)
+                                     const double *pxy, const double *t, int n, double *out, const ScaleDev *scl) {
+#define CALL(S) debug_sdf_at_s<S>(grid, lds, st, traj, sp, pxy, t, n, out, scl)
   SLICE_SWITCH(CALL)
 #undef CALL
 }

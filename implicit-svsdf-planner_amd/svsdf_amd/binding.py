@@ -31,7 +31,7 @@ EXPORTS = [
     "svsdf_mesh_outline", "svsdf_mesh_outline_obj", "svsdf_swept_outline", "svsdf_outline_extrude",
     "svsdf_get_plan", "svsdf_set_plan", "svsdf_set_combine", "svsdf_group_info", "svsdf_debug_sdf_at",
     "svsdf_group_stripe", "svsdf_set_group_serial", "svsdf_shape_selfcheck", "svsdf_mesh_section", "svsdf_mesh_section_obj",
-    "svsdf_last_launches",
+    "svsdf_last_launches", "svsdf_set_scale", "svsdf_get_scale",
 ]
 
 
@@ -91,7 +91,18 @@ class LaunchRec(C.Structure):
 
 
 LAUNCH_REC_CAP = 512     # SVSDF_LAUNCH_REC_CAP
-KERNELS = ["prep", "solve", "classify", "round", "tail", "reduce", "final", "finish"]   # svsdf_kernel_kind
+KERNELS = ["prep", "solve", "classify", "round", "tail", "reduce", "final", "finish",
+           "solve_scaled", "classify_scaled", "reduce_scaled"]   # svsdf_kernel_kind
+
+
+class Scale(C.Structure):
+    """svsdf_scale: s_a(t) = c[a] + sin(omega[a] t + phase[a]) amp[a] for a = x, y."""
+    _fields_ = [("struct_size", C.c_int), ("enabled", C.c_int), ("c", C.c_double * 2), ("amp", C.c_double * 2),
+                ("omega", C.c_double * 2), ("phase", C.c_double * 2)]
+
+
+# the reference's worked example (sw_manager.hpp:498-500): s_x = 0.8 + sin(1.5 t - 1.0) * 0.6, s_y = sin(1.8 t) * 0.4 + 0.8
+EXAMPLE_SCALE = {"c": (0.8, 0.8), "amp": (0.6, 0.4), "omega": (1.5, 1.8), "phase": (-1.0, 0.0)}
 
 
 class OutlineStats(C.Structure):
@@ -153,6 +164,8 @@ def lib():
     L.svsdf_query_points.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]
     L.svsdf_last_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.svsdf_last_launches.argtypes = [C.c_void_p, C.POINTER(LaunchRec), C.c_int, C.POINTER(C.c_int)]
+    L.svsdf_set_scale.argtypes = [C.c_void_p, C.POINTER(Scale)]
+    L.svsdf_get_scale.argtypes = [C.c_void_p, C.POINTER(Scale)]
     L.svsdf_shard_indices.argtypes = [C.c_void_p, C.POINTER(C.c_longlong)]
     L.svsdf_set_profiling.argtypes = [C.c_void_p, C.c_int]
     L.svsdf_shard_plan.argtypes = [_dp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong),
@@ -695,6 +708,28 @@ class SvsdfContext:
         self.L.svsdf_shape_selfcheck.argtypes = [C.c_void_p, _dp]
         self._chk(self.L.svsdf_shape_selfcheck(self.ctx, _p(o)), "svsdf_shape_selfcheck")
         return float(o[0]), float(o[1]), float(o[2])
+
+    def set_scale(self, c=None, amp=(0.0, 0.0), omega=(0.0, 0.0), phase=(0.0, 0.0), enabled=True, struct_size=None):
+        """Time-varying robot scale (svsdf_set_scale): s_a(t) = c[a] + sin(omega[a] t + phase[a]) amp[a], a = x, y.
+        c=None (or enabled=False) restores the rigid path; EXAMPLE_SCALE holds the reference's worked example."""
+        if c is None:
+            self._chk(self.L.svsdf_set_scale(self.ctx, None), "svsdf_set_scale")
+            return
+        s = Scale()
+        s.struct_size = C.sizeof(Scale) if struct_size is None else int(struct_size)
+        s.enabled = int(bool(enabled))
+        for name, v in (("c", c), ("amp", amp), ("omega", omega), ("phase", phase)):
+            getattr(s, name)[:] = [float(v[0]), float(v[1])]
+        self._chk(self.L.svsdf_set_scale(self.ctx, C.byref(s)), "svsdf_set_scale")
+
+    def get_scale(self):
+        """The schedule in force (svsdf_get_scale): None on the rigid path, else a dict c / amp / omega / phase."""
+        s = Scale()
+        s.struct_size = C.sizeof(Scale)
+        self._chk(self.L.svsdf_get_scale(self.ctx, C.byref(s)), "svsdf_get_scale")
+        if not s.enabled:
+            return None
+        return {k: (float(getattr(s, k)[0]), float(getattr(s, k)[1])) for k in ("c", "amp", "omega", "phase")}
 
     def get_plan(self):
         """Launch plan in force (svsdf_get_plan): bound_mode, batches, lanes_per_query, tail_iter, settled."""

@@ -55,6 +55,26 @@ class TrajOptimizer:
         self.combine = 0
         self._ctx = None
         self._points_dirty = True
+        self._scale = None             # setScale: the time-varying scale schedule (useScale + getScale), None: rigid
+
+    # -- SweptVolumeManager's useScale / getScale (sw_manager.hpp:17, 495-503) --
+    def setScale(self, scale=None):
+        """scale: None (rigid) or a dict c / amp / omega / phase (binding.EXAMPLE_SCALE: the reference's worked example).
+        Checked by the library at once; kept across context rebuilds."""
+        if self._ctx is not None:
+            if scale is None:
+                self._ctx.set_scale(None)
+            else:
+                self._ctx.set_scale(**scale)
+        elif scale is not None:
+            from .binding import FLAG_HOST_ONLY
+            probe = SvsdfContext(flags=FLAG_HOST_ONLY)   # the library's own checks, before any device context exists
+            probe.set_scale(**scale)
+            probe.close()
+        self._scale = None if scale is None else dict(scale)
+
+    def getScale(self):
+        return None if self._scale is None else dict(self._scale)
 
     # -- TrajOptimizer::setParam (reads Config; here a dict with the yaml keys) --
     def setParam(self, config):
@@ -109,6 +129,8 @@ class TrajOptimizer:
                                      head_state=self.initState, tail_state=self.finalState,
                                      device=self.device, rank=rank, world_size=ws,
                                      devices=self.devices, combine=self.combine, polygon_loops=polygon_loops)
+            if self._scale is not None:
+                self._ctx.set_scale(**self._scale)
             self._points_dirty = True
         if self._points_dirty:
             self._ctx.set_points(self.parallel_points)

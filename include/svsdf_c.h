@@ -423,7 +423,11 @@ enum svsdf_kernel_kind {
   SVSDF_KERNEL_TAIL = 4,      /* k_tail<shape, MODE, WAVES>: every GSIP iteration from `iter` on */
   SVSDF_KERNEL_REDUCE = 5,    /* k_reduce: assembly of the per-point terms (+ final sum when `fused`) */
   SVSDF_KERNEL_FINAL = 6,     /* k_final: fixed-order sum of the block partials */
-  SVSDF_KERNEL_FINISH = 7     /* k_finish: suffix sum and counters */
+  SVSDF_KERNEL_FINISH = 7,    /* k_finish: suffix sum and counters */
+  /* the scaled path (svsdf_set_scale): the launches that run S(t) arithmetic */
+  SVSDF_KERNEL_SOLVE_SCALED = 8,     /* k_solve_sc<shape, G>: rigid scan, scaled descent; G in {4, 8, 32} */
+  SVSDF_KERNEL_CLASSIFY_SCALED = 9,  /* k_classify_sc<shape>: exterior gradient at the scaled body-frame point */
+  SVSDF_KERNEL_REDUCE_SCALED = 10    /* k_reduce_sc: assembly with the position gradient under S(t*) */
 };
 typedef struct svsdf_launch_rec {
   int struct_size;      /* bytes of this record the library wrote (see svsdf_last_launches) */
@@ -451,6 +455,38 @@ typedef struct svsdf_launch_rec {
  * (a multi-device context returns SVSDF_ERR_INVALID). */
 int svsdf_last_launches(const svsdf_ctx *ctx, svsdf_launch_rec *out, int cap, int *count);
 
+/* Time-varying robot scale: the reference's useScale path (sw_manager.hpp:17, getScale :495-503).  With a schedule set,
+ * S(t) = diag(s_x(t), s_y(t), 1) with s_a(t) = c[a] + sin(omega[a] * t + phase[a]) * amp[a]  (a = 0: x, 1: y).
+ * The reference's worked example  s_x = 0.8 + sin(1.5 t - 1.0) * 0.6,  s_y = sin(1.8 t) * 0.4 + 0.8  is
+ * c = {0.8, 0.8}, amp = {0.6, 0.4}, omega = {1.5, 1.8}, phase = {-1.0, 0.0}, bit for bit; a constant scale is amp = 0.
+ * What the reference computes with useScale = true, and so what the library computes under a schedule:
+ *   - the seed scan (choiceTInit, all four layers) stays RIGID (sw_manager.hpp:567-570 call the rigid overloads);
+ *   - the descent (gradientDescent) evaluates the shape SDF at u = (Rt^T S(t)^-1) (p - x(t));
+ *   - the exterior gradient is the body-frame finite difference at that u at t*;
+ *   - the assembly's position gradient is -L' (-(S^-1)^T R g) at S(t*); the yaw gradient keeps the rigid form
+ *     (back_end_optimizer.hpp:1050, 1062).
+ * getDotScale / the analytic time derivative are never read on this path (sw_manager.hpp:806).
+ * Honoured by svsdf_eval_penalty(_partial), svsdf_lmbm_evaluate and the lmbm_* split, svsdf_query_points,
+ * svsdf_optimize_traj, svsdf_swept_outline and svsdf_debug_sdf_at (the scaled value and body-frame point).  The front-end
+ * entries (svsdf_check_sub_sw_collision, svsdf_shape_kernels) stay rigid, as in the reference.
+ * The scaled path runs a reduced launch plan: solve widths 4 / 8 / 32, the launch chain only (no fused tail), no culls, and
+ * every GSIP sample solved; svsdf_get_plan reports it.  The schedule belongs to the context: it survives svsdf_set_points /
+ * svsdf_set_conditions and reaches every device of a multi-device context.
+ * svsdf_set_scale(ctx, NULL) or enabled = 0 restores the rigid path.  SVSDF_ERR_INVALID with a message: struct_size is not
+ * sizeof(svsdf_scale), a non-finite parameter, or c[a] - |amp[a]| <= 0 (s_a(t) could reach 0: S singular, the case the
+ * reference warns about at sw_manager.hpp:493).  svsdf_get_scale needs out->struct_size = sizeof(svsdf_scale); with no
+ * schedule it reports enabled = 0 and the identity (c = 1, amp = 0). */
+typedef struct svsdf_scale {
+  int struct_size;     /* sizeof(svsdf_scale) */
+  int enabled;         /* 0: rigid (the same as NULL) */
+  double c[2];         /* c_x, c_y */
+  double amp[2];       /* A_x, A_y */
+  double omega[2];     /* w_x, w_y (rad / s) */
+  double phase[2];     /* phi_x, phi_y (rad) */
+} svsdf_scale;
+int svsdf_set_scale(svsdf_ctx *ctx, const svsdf_scale *scale);
+int svsdf_get_scale(const svsdf_ctx *ctx, svsdf_scale *out);
+
 /* Launch plan of the resident point set.  Every field only moves TIME: each setting returns the same bits (cost, gradient
  * and per-point results).  By default everything follows deterministic rules: the first evaluation
  * after svsdf_set_points runs with the cheap GSIP bound and decides the bound mode from its counters, the batch count
@@ -464,7 +500,8 @@ typedef struct svsdf_plan {
   int batches;          /* concurrent point batches 1..8; SVSDF_PLAN_AUTO: by rule; -2: measured (three HIP-event timings
                            per candidate count, best median) */
   int lanes_per_query;  /* lanes of the main solve's lane groups: 1, 2, 4, 8, 16, 32; SVSDF_PLAN_AUTO: by shard size */
-  int tail_iter;        /* GSIP iteration from which the fused tail kernel runs: >= 0; -2: never; SVSDF_PLAN_AUTO: by rule */
+  int tail_iter;        /* GSIP iteration from which the fused tail kernel runs: >= 0; -2: never; SVSDF_PLAN_AUTO: by rule
+                           (get under a scale schedule: -2, and lanes_per_query the scaled width 4 / 8 / 32) */
   int settled;          /* get only: 1 once nothing is left to decide for the resident point set */
 } svsdf_plan;
 int svsdf_get_plan(const svsdf_ctx *ctx, svsdf_plan *out);
@@ -508,7 +545,8 @@ int svsdf_set_profiling(svsdf_ctx *ctx, int enable);
 long long svsdf_debug_sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, int n);
 /* Diagnostic / test: getSDFAtTimeStamp<false> (sw_manager.hpp:741-750) of n (point, time) pairs on the device, through
  * the code the solve kernels inline.  points_xy: n x 2, t: n; out8: n x 8 = sdf, pose x, y, cos(yaw), sin(yaw), body-frame
- * x, y of the point, piece-time mode (0 cumulative, 1 / 2 the reference's chain).  The unit of work of the whole path:
+ * x, y of the point, piece-time mode (0 cumulative, 1 / 2 the reference's chain).  Under a scale schedule
+ * (svsdf_set_scale): getSDFAtTimeStamp<true>, the scaled sdf and the scaled body-frame point u.  The unit of work of the whole path:
  * tests compare it bit for bit with the oracle in device-arithmetic mode for every shape. */
 int svsdf_debug_sdf_at(svsdf_ctx *ctx, int N, const double *coeffs_colmajor, const double *T, size_t n,
                        const double *points_xy, const double *t, double *out8);

@@ -84,6 +84,36 @@ class TrajOptimizerHip {
   // members: context() compares them with what the live context was built from and rebuilds it on a mismatch.
   void resetContext() { svsdf_destroy(ctx_); ctx_ = nullptr; }
 
+  // useScale + getScale (sw_manager.hpp:17, 495-503): the time-varying scale schedule of this optimiser (svsdf_set_scale;
+  // nullptr or enabled = 0: rigid).  Checked by the library at once (on the live context, or on a host-only one when none
+  // exists yet); kept across context rebuilds.
+  int setScale(const svsdf_scale *s) {
+    int rc;
+    if (ctx_) {
+      rc = svsdf_set_scale(ctx_, s);
+    } else {
+      svsdf_config cfg;
+      svsdf_config_default(&cfg);
+      cfg.flags = SVSDF_FLAG_HOST_ONLY;
+      svsdf_ctx *probe = svsdf_create(&cfg);
+      if (!probe) return SVSDF_ERR_INVALID;
+      rc = svsdf_set_scale(probe, s);
+      svsdf_destroy(probe);
+    }
+    if (rc != SVSDF_OK) return rc;
+    has_scale_ = s != nullptr && s->enabled != 0;
+    if (has_scale_) scale_ = *s;
+    return SVSDF_OK;
+  }
+  int getScale(svsdf_scale *out) const {
+    if (!out || out->struct_size != (int)sizeof(svsdf_scale)) return SVSDF_ERR_INVALID;
+    if (has_scale_) { *out = scale_; return SVSDF_OK; }
+    *out = svsdf_scale{};
+    out->struct_size = (int)sizeof(svsdf_scale);
+    out->c[0] = out->c[1] = 1.0;
+    return SVSDF_OK;
+  }
+
   // static double costFunctionLmbmParallel(void *ptr, const double *x, double *g, const int n)
   static double costFunctionLmbmParallel(void *ptr, const double *x_variable, double *g, const int n) {
     TrajOptimizerHip &obj = *static_cast<TrajOptimizerHip *>(ptr);
@@ -211,6 +241,7 @@ class TrajOptimizerHip {
       cfg.polygon_nloops = (loop_sizes.size() >= 2) ? (int)loop_sizes.size() : 0;
       cfg.polygon_loop_sizes = (loop_sizes.size() >= 2) ? loop_sizes.data() : nullptr;
       ctx_ = svsdf_create(&cfg);
+      if (ctx_ && has_scale_ && svsdf_set_scale(ctx_, &scale_) != SVSDF_OK) { svsdf_destroy(ctx_); ctx_ = nullptr; }
       built_key_ = key;
       points_dirty_ = true;
     }
@@ -238,6 +269,8 @@ class TrajOptimizerHip {
   }
   std::string built_key_;
   svsdf_ctx *ctx_ = nullptr;
+  bool has_scale_ = false;
+  svsdf_scale scale_{};
   bool points_dirty_ = true;
 };
 
