@@ -1,6 +1,6 @@
 // svsdf_body_solve.hpp -- the body of k_solve and of the scaled k_solve_sc (svsdf_kernels.hpp), included inside both kernels
 // so that the rigid kernel is the very text it was before the scaled path existed (same instructions).  The including
-// kernel defines SC (constexpr bool) and scl (ScaleDev).  Not a header: no include guard, include nothing else.
+// kernel defines SC (constexpr bool), scl (ScaleDev) and ltab_g (layer pose tables or null).  Not a header: no include guard, include nothing else.
   extern __shared__ double solve_lds[];
   int n;
   const long long total = qs_total(qs, n);
@@ -28,7 +28,9 @@
 #define SVSDF_CLOCK_PROBE 1
 #endif
   const bool clk_probe = SVSDF_CLOCK_PROBE && work_idx == 0 && blockIdx.x == 0 && threadIdx.x < 64;   // (wave-uniform; BatchCtl::clk)
-  const long long clk_c0 = clk_probe ? clock64() : 0ll, clk_r0 = clk_probe ? wall_clock64() : 0ll;
+  // (the start values wait in the control block itself, not in four vector registers that would live through the whole kernel)
+  volatile unsigned long long *clk = ctl->clk;
+  if (clk_probe && threadIdx.x == 0) { clk[0] = (unsigned long long)clock64(); clk[1] = (unsigned long long)wall_clock64(); }
   // Work distribution: a wave's FIRST 64 / G queries are its own (wave index: no atomic), the following ones come from
   // the launch's cursor.  (All waves of a launch start together: with a fetch first, their 3000 atomics on one address
   // take ~ 12 ns each, one after the other -- the last wave would start ~ 37 us late, in every launch of the chain.)
@@ -37,6 +39,12 @@
   // takes the fused pass (derivative + both signs of the ladder in one step: descend_from_seed) instead of two dependent
   // steps per pass.  The chip has a wave slot for every query there; the launch is a chain of dependent evaluations.
   const bool solo = (prune & 2) != 0;
+  // `prune` bits 2 / 3: the launch carries the pose table of scan layer 2 / of layer 3 behind it (LayerTab, read by this wave only)
+  if ((threadIdx.x & 63) == 0) {
+    LayerTab *lt = wave_layer_tab<G>(wave_lds);
+    lt->l2 = (prune & 4) ? ltab_g : nullptr;
+    lt->l3 = (prune & 8) ? ltab_g + (size_t)K * kLayerSteps : nullptr;
+  }
   prune &= 1;
   const long long per_wave = solo ? 1 : 64 / G;
   const long long n_static = (long long)gridDim.x * (blockDim.x >> 6) * per_wave;
@@ -77,7 +85,7 @@
     const bool on = live && !culled;
     SVSDF_SITE_CYCLES(sc, 8, t_scan0);
     double x = 0.0, fx = 0.0;
-    descend_from_seed<SHAPE, G, U, SC>(tr, tk, sp, px, py, on, best_k, best_d, x, fx, n_eval, n_spec, sc, wave_lds, scl);   // whole wave
+    descend_from_seed<SHAPE, G, U, SC>(tr, tk, sp, px, py, on, best_k, best_d, x, fx, n_eval, n_spec, sc, wave_lds, scl, true);   // whole wave
     if (on && li == 0) {
       out_sdf[slot] = fx;
       out_t[slot] = x;
@@ -85,8 +93,8 @@
     }
   }
   if (clk_probe && threadIdx.x == 0) {
-    ctl->clk[0] = (unsigned long long)(clock64() - clk_c0);
-    ctl->clk[1] = (unsigned long long)(wall_clock64() - clk_r0);
+    clk[0] = (unsigned long long)clock64() - clk[0];
+    clk[1] = (unsigned long long)wall_clock64() - clk[1];
   }
   unsigned long long te = (unsigned long long)n_eval + n_scan, ts = n_solved, tc = n_scan, tu = n_culled, tp = n_spec;
 #pragma unroll

@@ -206,6 +206,7 @@ svsdf_ctx *svsdf_create(const svsdf_config *cfg) {
   if (const char *e = std::getenv("SVSDF_CULL")) { ctx->cull = std::atoi(e) != 0; ctx->cull2 = std::atoi(e) >= 2; }   // 0 none, 1 circle bound only, 2 both (default)
   if (const char *e = std::getenv("SVSDF_ROUND_BPC")) ctx->round_blocks_per_cu = std::max(1, std::min(std::atoi(e), 16));
   if (const char *e = std::getenv("SVSDF_SCAN_ANCHORS")) ctx->scan_anchors = std::atoi(e) != 0;
+  if (const char *e = std::getenv("SVSDF_LAYER_TABLES")) { const int v = std::atoi(e); ctx->layer_tables = (std::string(e) == "auto") ? -1 : (v == 0 || v == 2 || v == 3) ? v : -1; }
   if (const char *e = std::getenv("SVSDF_TAIL_DUO")) ctx->tail_duo = std::atoi(e) != 0;
   if (const char *e = std::getenv("SVSDF_TAIL_LOCAL")) ctx->tail_local = std::atoi(e) != 0;
   if (const char *e = std::getenv("SVSDF_TAIL_LATENCY")) ctx->tail_latency = std::atoi(e) != 0;
@@ -282,7 +283,7 @@ void svsdf_destroy(svsdf_ctx *ctx) {
   }
   (void)hipSetDevice(ctx->device);
   (void)hipDeviceSynchronize();
-  void *bufs[] = {ctx->d_poly, ctx->d_px, ctx->d_py, ctx->d_traj, ctx->d_in, ctx->d_pose, ctx->d_chunks,
+  void *bufs[] = {ctx->d_poly, ctx->d_px, ctx->d_py, ctx->d_traj, ctx->d_in, ctx->d_pose, ctx->d_chunks, ctx->d_ltab,
                   ctx->d_sdf, ctx->d_t, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy, ctx->gs.pt,
                   ctx->gs.r, ctx->gs.theta0, ctx->gs.theta_res, ctx->gs.iter, ctx->gs.nsamp, ctx->gs.phase, ctx->gs.req,
                   ctx->gs.list[0], ctx->gs.list[1], ctx->gs.solve, ctx->gs.sqx, ctx->gs.sqy, ctx->gs.sqth,
@@ -519,6 +520,7 @@ int svsdf_get_plan(const svsdf_ctx *ctx, svsdf_plan *out) {
   // (the scaled path: widths 4 / 8 / 32 and no fused tail, §4c; a width not chosen yet stays 0 = by shard size, as on the rigid path)
   out->lanes_per_query = (c->scaled && c->G > 0) ? svsdf::scaled_lanes(c->G) : c->G;
   out->tail_iter = (c->tail_mode == -2 || c->scaled) ? -2 : (c->tail_mode >= 0) ? c->tail_mode : (c->have_prev_nactive ? choose_tail_iter(c) : SVSDF_PLAN_AUTO);
+  out->layer_tables = c->layer_tables;
   out->settled = ((c->ub_env || c->ub_tune > 0) && c->bt_state == 0 && c->an_state == 0 && c->lz_state == 0 && c->have_prev_nsolve) ? 1 : 0;
   return SVSDF_OK;
 }
@@ -527,7 +529,8 @@ int svsdf_set_plan(svsdf_ctx *ctx, const svsdf_plan *plan) {
   if (!ctx || !plan) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_set_plan: null argument");
   const int g = plan->lanes_per_query;
   if (plan->bound_mode < SVSDF_PLAN_AUTO || plan->bound_mode > 3 || plan->batches < -2 || plan->batches == 0 || plan->batches > kMaxBatches ||
-      !(g == SVSDF_PLAN_AUTO || g == 1 || g == 2 || g == 4 || g == 8 || g == 16 || g == 32) || plan->tail_iter < -2 || plan->tail_iter >= kMaxIter)
+      !(g == SVSDF_PLAN_AUTO || g == 1 || g == 2 || g == 4 || g == 8 || g == 16 || g == 32) || plan->tail_iter < -2 || plan->tail_iter >= kMaxIter ||
+      !(plan->layer_tables == SVSDF_PLAN_AUTO || plan->layer_tables == 0 || plan->layer_tables == 2 || plan->layer_tables == 3))
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_set_plan: field out of range");
   if (!ctx->subs.empty()) {
     int rc = SVSDF_OK;
@@ -536,6 +539,7 @@ int svsdf_set_plan(svsdf_ctx *ctx, const svsdf_plan *plan) {
   }
   if (ctx->host_only) return SVSDF_OK;
   HIPCHK(hipSetDevice(ctx->device));
+  ctx->layer_tables = plan->layer_tables;
   // bound mode: a change invalidates the launch widths on record (they belong to the other mode's solve counts)
   if (plan->bound_mode == SVSDF_PLAN_AUTO) {
     if (ctx->ub_env) { ctx->ub_env = false; ctx->ub_tune = 0; ctx->have_prev_nsolve = false; ctx->have_prev_nactive = false; }

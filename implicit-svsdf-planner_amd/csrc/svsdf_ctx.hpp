@@ -104,6 +104,12 @@ struct svsdf_ctx {
   svsdf::Pose *d_pose = nullptr;
   svsdf::Chunk *d_chunks = nullptr;
   size_t pose_cap = 0;
+  // pose tables of scan layers 2 and 3 (k_layer_tables): layer 2's K x 21 poses, layer 3's K x 22 x 21 behind them
+  svsdf::Pose *d_ltab = nullptr;
+  size_t ltab_cap = 0;         // seeds (K) the buffer holds; grown on demand, never per evaluation
+  int layer_tables = -1;       // plan: -1 by the previous evaluation's solve count, 0 off, 2 layer 2 only, 3 layers 2 and 3 (env SVSDF_LAYER_TABLES; same results)
+  int ltab_mode = 0;           // this evaluation: 0 none built, 2 / 3 as above
+  long long prev_solves = 0;   // argmin solves of the previous evaluation (valid with have_prev_nsolve)
   double r_bound = 0.0;    // shape bound radius for the layer-1 chunk pruning (analytic circumradius + offset)
   double r_bound_sampled = 0.0;  // max over a polar grid of |q| - sdf(q): self-check, must not exceed r_bound
   double lipschitz_excess = 0.0; // largest |f(q') - f(q)| - |q' - q| found by the same grid (k_rbound); must be <= 0

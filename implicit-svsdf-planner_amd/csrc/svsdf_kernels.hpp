@@ -61,6 +61,14 @@ struct TrajDev {
 };
 
 struct Pose { double x, y, cs, sn; };
+// Pose tables of choiceTInit's layers 2 and 3 (k_layer_tables).  The sample times of layer 2 depend on the
+// layer-1 seed index best_k alone, those of layer 3 on (best_k, w2), w2 = layer 2's winning sample or none: a window holds
+// at most kLayerSteps samples (t0 + i dt <= seed + 10 dt).  l2[k * 21 + i], l3[(k * 22 + (w2 + 1)) * 21 + i]; a null
+// pointer means the lanes compute that layer's poses themselves.  A wave keeps the two pointers in its LDS (behind the
+// ladder state, ladder_lds_bytes) and reads them where a layer starts: k_solve has no scalar register to spare, and a
+// wave-uniform value that lives through the whole kernel ends up occupying vector registers.
+constexpr int kLayerSteps = 21;
+struct LayerTab { const Pose *l2, *l3; };
 
 // Layer-1 pruning: bounding circle of the robot-origin positions of kChunk consecutive scan
 // samples, inflated by the shape's bound radius R (sdf_shape(q) >= |q| - R for every q), so
@@ -596,6 +604,47 @@ __global__ void __launch_bounds__(1024) k_prep(const double *__restrict__ in, in
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// k_layer_tables: the poses of choiceTInit's layers 2 and 3 for every window a query can ask for (LayerTab), one entry per
+// thread.  Row r of seed k: r = 0 layer 2 around tk[k]; r = 1 layer 3 around the unchanged seed (no sample of layer 2 beat
+// the carried minimum); r = 2 + w layer 3 around the time of layer 2's sample w.  Every time is produced by the additions
+// descend_from_seed makes (t0, then += dt one at a time; dt = 0.15, *= 0.1 per layer) and every pose by the same pose_at
+// in the launch's piece-time mode, so an entry is bit for bit what the lane would have computed.  Entries past a window's
+// loop_terminal are not written (nor read).  Launched after k_prep on the same stream (TrajDev, tk).
+// ---------------------------------------------------------------------------------------------
+constexpr int kLayerRows = kLayerSteps + 2;
+__global__ void __launch_bounds__(256) k_layer_tables(const TrajDev *__restrict__ trg, const double *__restrict__ tk, int K,
+                                                      int rows /* 1: layer 2 only */, Pose *__restrict__ out) {
+  extern __shared__ double lt_lds[];
+  const TrajL tr = stage_traj(trg, lt_lds);   // ends with __syncthreads
+  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long long)K * rows * kLayerSteps) return;
+  const int i = (int)(e % kLayerSteps), r = (int)((e / kLayerSteps) % rows), k = (int)(e / ((long long)kLayerSteps * rows));
+  double seed = tk[k];
+  double dt = 0.15;
+  dt *= 0.1;
+  if (r > 0) {
+    if (r >= 2) {   // layer 2's sample r - 2 hands its time on
+      const double t0 = dmax(0.0, seed - 10 * dt);
+      const double loop_terminal = dmin(tr.dur, seed + 10 * dt);
+      double t = t0;
+      for (int j = 0; j < r - 2; ++j) t += dt;
+      if (!(t <= loop_terminal)) return;
+      seed = t;
+    }
+    dt *= 0.1;
+  }
+  const double t0 = dmax(0.0, seed - 10 * dt);
+  const double loop_terminal = dmin(tr.dur, seed + 10 * dt);
+  double t = t0;
+  for (int j = 0; j < i; ++j) t += dt;
+  if (!(t <= loop_terminal)) return;
+  PieceCache pc = piece_cache_init();
+  Pose *dst = (r == 0) ? out + (size_t)k * kLayerSteps
+                       : out + (size_t)K * kLayerSteps + ((size_t)k * (kLayerSteps + 1) + (size_t)(r - 1)) * kLayerSteps;
+  dst[i] = pose_at(tr, t, pc);
+}
+
 #endif  // SVSDF_API_TU
 
 // Shape bound radius: max over a polar grid of |q| - sdf_shape(q) (body frame, including the
@@ -1020,7 +1069,11 @@ __device__ __forceinline__ void scan_layer1(const ShapeParams &sp, const Pose *p
 // descent is shared out over the whole wave (SVSDF_ELASTIC, below; wave_lds: this wave's ladder_lds_bytes(G) of LDS).
 // (80-byte rows: 20 dwords, so the rows of 16 groups start in 16 different LDS banks)
 struct alignas(16) LadderState { double px, py, seed, x, fx, prev_x, lo, hi; int sgn, piece, pad_[2]; };   // one group's descent
-__host__ __device__ constexpr size_t ladder_lds_bytes(int G) { return (size_t)(64 / G) * sizeof(LadderState) + 64; }
+__host__ __device__ constexpr size_t ladder_lds_bytes(int G) { return (size_t)(64 / G) * sizeof(LadderState) + 64 + sizeof(LayerTab); }
+template <int G>
+__device__ __forceinline__ LayerTab *wave_layer_tab(void *wave_lds) {   // behind the ladder rows and their 64-byte lane map
+  return reinterpret_cast<LayerTab *>(reinterpret_cast<char *>(wave_lds) + (size_t)(64 / G) * sizeof(LadderState) + 64);
+}
 // SC (the scaled path, §4c): the descent's evaluations -- candidates, the two-time-point finite difference, both signs of
 // the fused ladder -- take S(t); layers 2-4 stay rigid like the reference's choiceTInit (SWM:567-570).  The first pass
 // evaluates f(x) itself, so no rigid scan value is ever taken for a descent value.
@@ -1028,7 +1081,8 @@ template <int SHAPE, int G, int U, bool SC = false>
 __device__ __forceinline__ void descend_from_seed(const TrajL &tr, const double *__restrict__ tk, const ShapeParams &sp,
                                                   double px, double py, bool on, int best_k, double best_d,
                                                   double &x_out, double &fx_out, unsigned &n_eval, unsigned &n_spec,
-                                                  unsigned long long (&sc)[12], void *wave_lds, const ScaleDev &scl = ScaleDev{}) {
+                                                  unsigned long long (&sc)[12], void *wave_lds, const ScaleDev &scl = ScaleDev{},
+                                                  bool tables = false /* constant: the wave's LayerTab is set */) {
   const int li = Grp<G>::li();
   const double inf = __longlong_as_double(0x7ff0000000000000ll);
     PieceCache piece = piece_cache_init();
@@ -1042,7 +1096,78 @@ __device__ __forceinline__ void descend_from_seed(const TrajL &tr, const double 
     constexpr int W = G * U;
     double dt = 0.15;
     dt *= 0.1;
-    for (int layer = 2; layer <= 4; ++layer) {
+    // Layers 2 and 3 from the launch's pose tables (LayerTab): which sample wins depends on the query, the sample times --
+    // and so the poses -- only on best_k and on w2, layer 2's winning sample (-1: none beat the seed).  The lanes keep
+    // accumulating t (the winner's time and the trip count need it); only the pose comes from the table.  Not for the
+    // Polygon kernels: they sit at their register cap and the extra state would go to scratch (tests/test_kernel_resources.py).
+    constexpr bool kTables = !is_polygon<SHAPE>();
+    int layer = 2;
+    if (kTables && tables) {
+      int w2 = -1;
+#pragma nounroll
+      for (; layer <= 3; ++layer) {
+        const LayerTab *lt = wave_layer_tab<G>(wave_lds);
+        typedef const __attribute__((address_space(1))) char *GlobalBytes;   // (a pointer read from LDS: say that it is global memory)
+        const GlobalBytes tab = (GlobalBytes)((layer == 2) ? lt->l2 : lt->l3);
+        if (tab == nullptr) break;   // wave-uniform
+        const double t0 = dmax(0.0, time_seed - 10 * dt);
+        const double loop_terminal = dmin(tr.dur, time_seed + 10 * dt);
+        // (a 32-bit byte offset from the table: at most 16000 x 22 x 21 entries of 32 bytes)
+        unsigned off = (unsigned)(((layer == 2) ? best_k : best_k * (kLayerSteps + 1) + (w2 + 1)) * kLayerSteps + li) * (unsigned)sizeof(Pose);
+        const auto entry = [tab](unsigned o) {
+          const __attribute__((address_space(1))) double *e = reinterpret_cast<const __attribute__((address_space(1))) double *>(tab + o);
+          return Pose{e[0], e[1], e[2], e[3]};
+        };
+        double t[U];
+        t[0] = t0;
+        for (int i = 0; i < li; ++i) t[0] += dt;   // the li-th accumulated sample
+#pragma unroll
+        for (int u = 1; u < U; ++u) {
+          t[u] = t[u - 1];
+#pragma unroll
+          for (int i = 0; i < G; ++i) t[u] += dt;
+        }
+        int kbase = 0;
+        // the loads of a layer's steps do not depend on each other: the next step's is issued before this one is evaluated
+        Pose pn[U] = {};
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (t[u] <= loop_terminal) pn[u] = entry(off + (unsigned)(G * u * sizeof(Pose)));
+        }
+        while (Grp<G>::bcast(t[0], 0) <= loop_terminal) {
+          double d[U], tc[U];
+          Pose pc[U];
+          off += (unsigned)(W * sizeof(Pose));
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            tc[u] = t[u];
+            pc[u] = pn[u];
+#pragma unroll
+            for (int i = 0; i < W; ++i) t[u] += dt;
+            if (t[u] <= loop_terminal) pn[u] = entry(off + (unsigned)(G * u * sizeof(Pose)));
+          }
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            d[u] = inf;
+            SVSDF_SITE(sc, 1, tc[u] <= loop_terminal);
+            if (tc[u] <= loop_terminal) { d[u] = sdf_from_pose<SHAPE>(sp, pc[u], px, py); ++n_eval; }
+          }
+          double db = d[0], tb = tc[0];
+          int k = kbase + li;
+#pragma unroll
+          for (int u = 1; u < U; ++u)
+            if (d[u] < db) { db = d[u]; tb = tc[u]; k = kbase + li + G * u; }  // strict: earliest kept
+          const int kmine = k;
+          Grp<G>::min_dk(db, k);
+          const int src = (k - kbase) % G;
+          const double tw = Grp<G>::bcast((k == kmine) ? tb : 0.0, src);
+          if (db < min_dis) { time_seed = tw; min_dis = db; w2 = k; }
+          kbase += W;
+        }
+        dt *= 0.1;
+      }
+    }
+    for (int left = 5 - layer; left > 0; --left) {   // the layers the tables did not serve
       const double t0 = dmax(0.0, time_seed - 10 * dt);
       const double loop_terminal = dmin(tr.dur, time_seed + 10 * dt);
       double t[U];
@@ -1385,8 +1510,8 @@ template <int SHAPE, int G, int U>
 __global__ void __launch_bounds__(kBlock, is_polygon<SHAPE>() ? 3 : SVSDF_SOLVE_WAVES)
 k_solve(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Pose *__restrict__ pose_g,
         const Chunk *__restrict__ chunks_g, ShapeParams sp, QuerySet qs, double *__restrict__ out_sdf,
-        double *__restrict__ out_t, int prune /* bit 0: exact chunk pruning; bit 1: one query per wave */, BatchCtl *__restrict__ ctl, int work_idx, double cull_thresh,
-        const double *__restrict__ rot, double slack_max) {
+        double *__restrict__ out_t, int prune /* bit 0: exact chunk pruning; bit 1: one query per wave; bits 2, 3: layer tables */, BatchCtl *__restrict__ ctl, int work_idx, double cull_thresh,
+        const double *__restrict__ rot, double slack_max, const Pose *__restrict__ ltab_g) {
   constexpr bool SC = false;
   const ScaleDev scl{};
 #include "svsdf_body_solve.hpp"
@@ -1399,7 +1524,7 @@ __global__ void __launch_bounds__(kBlock, is_polygon<SHAPE>() ? 3 : SVSDF_SOLVE_
 k_solve_sc(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Pose *__restrict__ pose_g,
            const Chunk *__restrict__ chunks_g, ShapeParams sp, QuerySet qs, double *__restrict__ out_sdf,
            double *__restrict__ out_t, int prune, BatchCtl *__restrict__ ctl, int work_idx, double cull_thresh,
-           const double *__restrict__ rot, double slack_max, ScaleDev scl) {
+           const double *__restrict__ rot, double slack_max, ScaleDev scl, const Pose *__restrict__ ltab_g) {
   constexpr bool SC = true;
 #include "svsdf_body_solve.hpp"
 }

@@ -18,6 +18,7 @@ struct SolveLaunch {   // arguments of k_solve<SHAPE, G, 1>
   double *out_sdf, *out_t; int prune; BatchCtl *ctl; int work_idx; double cull_thresh;
   const double *rot; double slack_max;   // second exact cull (main points): per-chunk yaw allowance W_c h, max_c of the linear one
   const ScaleDev *scl = nullptr;         // not null: k_solve_sc<SHAPE, G, 1> under this scale schedule (G in kScaledLanes)
+  const Pose *ltab = nullptr;            // layer-2 pose table, layer 3's behind it (k_layer_tables); `prune` bits 2 / 3 say which the launch uses
 };
 struct RoundLaunch {   // arguments of k_round<SHAPE, LP, MODE>
   const TrajDev *traj; const Pose *pose; const Chunk *chunks; ShapeParams sp; const double *px, *py; GsipState gs;

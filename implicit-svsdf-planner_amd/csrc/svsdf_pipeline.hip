@@ -209,8 +209,8 @@ void launch_solve(svsdf_ctx *ctx, int G, hipStream_t st, const QuerySet &qs, lon
   // (the second, value-based cull runs with the first one: main points of an evaluation that may cull)
   const bool cull2 = std::isfinite(cull_thresh) && ctx->cull2;
   const double *d_rot = d_tk + ctx->K + (ctx->K + kChunk - 1) / kChunk;
-  const SolveLaunch a{ctx->d_traj, d_tk, ctx->d_pose, ctx->d_chunks, ctx->sp, qs, out_sdf, out_t, ctx->prune | (solo ? 2 : 0), ctl, work_idx, cull_thresh,
-                      cull2 ? d_rot : nullptr, ctx->slack_max, ctx->scaled ? &ctx->scale : nullptr};
+  const SolveLaunch a{ctx->d_traj, d_tk, ctx->d_pose, ctx->d_chunks, ctx->sp, qs, out_sdf, out_t, ctx->prune | (solo ? 2 : 0) | (ctx->ltab_mode >= 2 ? 4 : 0) | (ctx->ltab_mode >= 3 ? 8 : 0), ctl, work_idx, cull_thresh,
+                      cull2 ? d_rot : nullptr, ctx->slack_max, ctx->scaled ? &ctx->scale : nullptr, ctx->d_ltab};
   const int shape = poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
   if (!launch_k_solve(shape, G, grid, (unsigned)blk, lds_total, st, a) && ctx->launch_err.empty())
     ctx->launch_err = "k_solve: shape not compiled into this build";
@@ -498,6 +498,38 @@ int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bo
                      ctx->piece_time_mode, ctx->d_traj,
                      ctx->d_pose, ctx->d_chunks, ctx->r_bound, ctx->d_ctl, ctx->nbatch, clear_nonfinite ? ctx->d_nonfinite : nullptr);
   (void)record_launch(ctx, SVSDF_KERNEL_PREP, -1, 1, 1024, lds, (long long)K, 0);
+  ctx->ltab_mode = 0;   // (the tables on the device belong to the previous trajectory: build_layer_tables)
+  return SVSDF_OK;
+}
+
+// Pose tables of scan layers 2 and 3 for this evaluation's argmin solves (k_layer_tables; main stream, after k_prep and
+// before the batches fork).  A solve reads 2 x 21 poses from them instead of computing them; building them costs
+// K x 23 x 21 pose evaluations and a launch.  Rule (plan field layer_tables, env SVSDF_LAYER_TABLES pin it): build when the
+// poses the solves save are at least 16 times the poses the tables hold, with the solve count of the previous
+// evaluation of this point set (the point count before there is one) -- 184 K solves, 98 k at 32 pieces, where the
+// launch is ~ 2 % of the evaluation.  A reference-scale callback (hundreds of points) never builds them.
+int build_layer_tables(svsdf_ctx *ctx) {
+  int mode = ctx->layer_tables;
+  const size_t K = (size_t)ctx->K;
+  if (mode < 0) {
+    const long long solves = ctx->have_prev_nsolve ? ctx->prev_solves : (long long)ctx->P;
+    mode = (solves * 2 * svsdf::kLayerSteps >= 16ll * (long long)K * svsdf::kLayerRows * svsdf::kLayerSteps) ? 3 : 0;
+  }
+  if (ctx->cfg.shape_id == (int)svsdf::kPolygon) mode = 0;   // the Polygon kernels compute every layer (descend_from_seed)
+  if (mode == 0) return SVSDF_OK;
+  if (K > ctx->ltab_cap) {
+    const size_t cap = K + 256;
+    ctx->ltab_cap = 0;
+    int rc = dev_alloc(ctx, &ctx->d_ltab, cap * (size_t)svsdf::kLayerRows * svsdf::kLayerSteps);
+    if (rc) return rc;
+    ctx->ltab_cap = cap;
+  }
+  const int rows = (mode >= 3) ? svsdf::kLayerRows : 1;
+  const size_t lds = (size_t)traj_lds_doubles(ctx->N) * sizeof(double);
+  const unsigned grid = (unsigned)((K * (size_t)rows * svsdf::kLayerSteps + 255) / 256);
+  hipLaunchKernelGGL(k_layer_tables, dim3(grid), dim3(256), lds, ctx->stream, ctx->d_traj, ctx->d_in + 19 * (size_t)ctx->N, (int)K, rows, ctx->d_ltab);
+  if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_LAYER_TABLES, -1, grid, 256, lds, (long long)(K * rows * svsdf::kLayerSteps), 0)) r->targ[0] = mode;
+  ctx->ltab_mode = mode;
   return SVSDF_OK;
 }
 
@@ -570,6 +602,7 @@ int enqueue_queries(svsdf_ctx *ctx, int N, const double *coeffs, const double *T
   (void)hipEventRecord(ctx->ev_pool[e_begin], ctx->stream);
   int rc = upload_traj(ctx, N, coeffs, T, /*clear_nonfinite=*/true);   // (k_prep also clears the non-finite counter)
   if (rc) return rc;
+  if ((rc = build_layer_tables(ctx))) return rc;
   const bool fork = ctx->nbatch > 1;   // one batch: the whole chain stays on the main stream (no cross-stream hand-offs)
   if (fork) HIPCHK(hipEventRecord(ctx->ev_prep, ctx->stream));
   const int m = ctx->tail_iter = choose_tail_iter(ctx);
@@ -614,6 +647,7 @@ int swept_field(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, do
   reset_launches(ctx);
   int rc = upload_traj(ctx, N, coeffs, T);
   if (rc) return rc;
+  if ((rc = build_layer_tables(ctx))) return rc;
   if (ctx->nbatch > 1) HIPCHK(hipEventRecord(ctx->ev_prep, ctx->stream));
   for (int b = 0; b < ctx->nbatch; ++b) {
     hipStream_t st = batch_stream(ctx, b);
@@ -734,6 +768,7 @@ int finish(svsdf_ctx *ctx, bool with_partial) {
     ctx->stats.shader_clock_mhz = r ? (double)c / (double)r * ctx->wall_clock_khz * 1e-3 : 0.0;
   }
   for (int i = 0; i < kMaxIter; ++i) ctx->prev_nsolve[i] = (long long)st[9 + i];
+  ctx->prev_solves = (long long)st[0];
   ctx->have_prev_nsolve = true;
   for (int i = 0; i < kMaxIter; ++i) ctx->prev_nactive[i] = (long long)st[11 + kMaxIter + i];
   ctx->prev_tail_iter = ctx->tail_iter;

@@ -76,7 +76,7 @@ class Stats(C.Structure):
 
 class Plan(C.Structure):
     _fields_ = [("bound_mode", C.c_int), ("batches", C.c_int), ("lanes_per_query", C.c_int), ("tail_iter", C.c_int),
-                ("settled", C.c_int)]
+                ("settled", C.c_int), ("layer_tables", C.c_int)]
 
 
 PLAN_AUTO = -1
@@ -92,7 +92,7 @@ class LaunchRec(C.Structure):
 
 LAUNCH_REC_CAP = 512     # SVSDF_LAUNCH_REC_CAP
 KERNELS = ["prep", "solve", "classify", "round", "tail", "reduce", "final", "finish",
-           "solve_scaled", "classify_scaled", "reduce_scaled"]   # svsdf_kernel_kind
+           "solve_scaled", "classify_scaled", "reduce_scaled", "layer_tables"]   # svsdf_kernel_kind
 
 
 class Scale(C.Structure):
@@ -732,15 +732,16 @@ class SvsdfContext:
         return {k: (float(getattr(s, k)[0]), float(getattr(s, k)[1])) for k in ("c", "amp", "omega", "phase")}
 
     def get_plan(self):
-        """Launch plan in force (svsdf_get_plan): bound_mode, batches, lanes_per_query, tail_iter, settled."""
+        """Launch plan in force (svsdf_get_plan): bound_mode, batches, lanes_per_query, tail_iter, settled, layer_tables."""
         pl = Plan()
         self._chk(self.L.svsdf_get_plan(self.ctx, C.byref(pl)), "svsdf_get_plan")
         return {k: getattr(pl, k) for k, _ in Plan._fields_}
 
-    def set_plan(self, bound_mode=PLAN_AUTO, batches=PLAN_AUTO, lanes_per_query=PLAN_AUTO, tail_iter=PLAN_AUTO):
+    def set_plan(self, bound_mode=PLAN_AUTO, batches=PLAN_AUTO, lanes_per_query=PLAN_AUTO, tail_iter=PLAN_AUTO,
+                 layer_tables=PLAN_AUTO):
         """Pin fields of the launch plan (svsdf_set_plan; PLAN_AUTO leaves a field to its rule; batches=-2: measured).
         Only moves time: every plan returns the same bits."""
-        pl = Plan(int(bound_mode), int(batches), int(lanes_per_query), int(tail_iter), 0)
+        pl = Plan(int(bound_mode), int(batches), int(lanes_per_query), int(tail_iter), 0, int(layer_tables))
         self._chk(self.L.svsdf_set_plan(self.ctx, C.byref(pl)), "svsdf_set_plan")
 
     def set_combine(self, combine):

@@ -427,7 +427,8 @@ enum svsdf_kernel_kind {
   /* the scaled path (svsdf_set_scale): the launches that run S(t) arithmetic */
   SVSDF_KERNEL_SOLVE_SCALED = 8,     /* k_solve_sc<shape, G>: rigid scan, scaled descent; G in {4, 8, 32} */
   SVSDF_KERNEL_CLASSIFY_SCALED = 9,  /* k_classify_sc<shape>: exterior gradient at the scaled body-frame point */
-  SVSDF_KERNEL_REDUCE_SCALED = 10    /* k_reduce_sc: assembly with the position gradient under S(t*) */
+  SVSDF_KERNEL_REDUCE_SCALED = 10,   /* k_reduce_sc: assembly with the position gradient under S(t*) */
+  SVSDF_KERNEL_LAYER_TABLES = 11     /* k_layer_tables: pose tables of scan layers 2 / 3 (targ[0]: 2 or 3; only when the plan builds them) */
 };
 typedef struct svsdf_launch_rec {
   int struct_size;      /* bytes of this record the library wrote (see svsdf_last_launches) */
@@ -503,6 +504,8 @@ typedef struct svsdf_plan {
   int tail_iter;        /* GSIP iteration from which the fused tail kernel runs: >= 0; -2: never; SVSDF_PLAN_AUTO: by rule
                            (get under a scale schedule: -2, and lanes_per_query the scaled width 4 / 8 / 32) */
   int settled;          /* get only: 1 once nothing is left to decide for the resident point set */
+  int layer_tables;     /* pose tables of scan layers 2 / 3 for the argmin solves: 0 none, 2 layer 2, 3 layers 2 and 3;
+                           SVSDF_PLAN_AUTO: both when the previous evaluation's solve count pays for building them */
 } svsdf_plan;
 int svsdf_get_plan(const svsdf_ctx *ctx, svsdf_plan *out);
 int svsdf_set_plan(svsdf_ctx *ctx, const svsdf_plan *plan);
