@@ -54,6 +54,10 @@ def lib():
     L.orc_traj_vel.argtypes = [C.c_void_p, C.c_double, _dp]
     L.orc_sdf_at_time.restype = C.c_double
     L.orc_sdf_at_time.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double]
+    L.orc_set_scale.restype = None
+    L.orc_set_scale.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int]
+    L.orc_rel_at_time.restype = None
+    L.orc_rel_at_time.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, _dp]
     L.orc_sdf_swept.restype = C.c_double
     L.orc_shape_eval_batch.argtypes = [C.c_void_p, _dp, C.c_size_t, _dp, _dp]
     L.orc_shape_eval_batch.restype = None
@@ -149,6 +153,27 @@ class Oracle:
 
     def sdf_at_time(self, px, py, t):
         return self.L.orc_sdf_at_time(self.ctx, px, py, t)
+
+    def set_scale(self, c=None, amp=(0.0, 0.0), omega=(0.0, 0.0), phase=(0.0, 0.0)):
+        """The reference's useScale path with s_a(t) = c_a + sin(omega_a t + phase_a) amp_a (the signature of
+        SvsdfContext.set_scale); c=None clears the schedule: the rigid path, with the bits it always had."""
+        if c is None:
+            self.L.orc_set_scale(self.ctx, None, None, None, None, 0)
+            return
+        v = [_f64(a).reshape(2) for a in (c, amp, omega, phase)]
+        if not all(np.isfinite(a).all() for a in v) or np.any(v[0] - np.abs(v[1]) <= 0.0):
+            raise ValueError("scale schedule: finite parameters with c - |amp| > 0 (S must stay invertible)")
+        self.L.orc_set_scale(self.ctx, _p(v[0]), _p(v[1]), _p(v[2]), _p(v[3]), 1)
+
+    def rel_at_time(self, pxy, t):
+        """(sdf, u_x, u_y) of the SDF-at-a-time evaluation at (n, 2) points and n times, under the schedule and modes."""
+        pxy, t = _f64(pxy).reshape(-1, 2), _f64(t).reshape(-1)
+        out = np.zeros((len(t), 3))
+        row = np.zeros(3)
+        for k in range(len(t)):
+            self.L.orc_rel_at_time(self.ctx, pxy[k, 0], pxy[k, 1], t[k], _p(row))
+            out[k] = row
+        return out
 
     def shape_eval(self, xy, grad=False):
         """Raw body-frame getonlySDF (and getonlyGrad1) of this oracle's shape at (P, 2) points."""

@@ -28,6 +28,11 @@ struct orc_ctx {
   int trig_mode; /* 0: libm sin/cos/atan2 (the reference's arithmetic); 1: the ROCm device library's algorithms;
                     2: libm results moved by -1 / 0 / +1 ulp, pseudo-randomly per argument (orc_set_trig_perturb) */
   unsigned long long trig_seed;
+  /* time-varying robot scale (the reference's useScale = true, SWM:17): S(t) = diag(s_x(t), s_y(t), 1),
+   * s_a(t) = c_a + sin(w_a t + phi_a) A_a -- the form of getScale's worked schedule (SWM:495-503).  Per context: the
+   * OpenMP loops read the context as const.  use_scale = 0: the rigid code below runs as it always did. */
+  int use_scale;
+  double sc_c[2], sc_amp[2], sc_omega[2], sc_phase[2];
 };
 
 /* thread-local work counters, folded into ctx->cnt by the entry points */
@@ -616,6 +621,14 @@ static inline double trig_atan2(const orc_ctx *ctx, double y, double x) {
   const double v = atan2(y, x);
   return ctx->trig_mode == 2 ? ulp_nudge(v, dbits(y) ^ (dbits(x) * 0x9e3779b97f4a7c15ULL) ^ ctx->trig_seed) : v;
 }
+/* the scale schedule's sine (getScale SWM:495-503: sin(1.5*t-1.0), a call of its own -- no cosine of the same argument to
+ * merge it with).  Mode 1: the device calls sin(), whose small-argument path in the device library is the reduction and the
+ * sincosred2 kernel of sincos (__ocml_sin_f64 = trigredsmall + sincosred2, the sine selected by the quadrant). */
+static inline double trig_sin(const orc_ctx *ctx, double a) {
+  if (ctx->trig_mode == 1) { double sn, cs; dev_sincos(a, &sn, &cs); return sn; }
+  const double v = sin(a);
+  return ctx->trig_mode == 2 ? ulp_nudge(v, dbits(a) ^ (ctx->trig_seed * 0x9e3779b97f4a7c15ULL + 2ULL)) : v;
+}
 void orc_set_trig_perturb(orc_ctx *ctx, unsigned long long seed) {
   /* libm trig moved by <= 1 ulp (seeded), the reference's piece location: a third oracle for the sensitivity bracket */
   ctx->trig_mode = 2;
@@ -635,9 +648,33 @@ void orc_set_trig_mode(orc_ctx *ctx, int mode) {
 /* ------------------------------------------------------------------------- */
 /* SDF at a time stamp, argmin over t                                         */
 /* ------------------------------------------------------------------------- */
+/* getScale SWM:495-503 and its inverse as posEva2Rel takes it (St.inverse(), SWM:528-535).  Eigen's 3x3 inverse() is
+ * cofactors times 1 / det: for the diagonal S, det = s_y s_x (+ exact zeros), i00 = s_y invdet, i11 = s_x invdet -- not
+ * 1 / s_x, 1 / s_y.  S = I gives exactly 1, 1. */
+static inline void scale_inv(const orc_ctx *ctx, double t, double *i00, double *i11) {
+  const double sx = ctx->sc_c[0] + trig_sin(ctx, ctx->sc_omega[0] * t + ctx->sc_phase[0]) * ctx->sc_amp[0];
+  const double sy = ctx->sc_c[1] + trig_sin(ctx, ctx->sc_omega[1] * t + ctx->sc_phase[1]) * ctx->sc_amp[1];
+  const double invdet = 1.0 / (sy * sx);
+  *i00 = sy * invdet;
+  *i11 = sx * invdet;
+}
+/* getStateOnTrajStamp with St SWM:476-487 + posEva2Rel(pos_eva, xt, Rt, St) SWM:528-535: (Rt^T St^-1) is formed as a
+ * matrix first, then times (p - xt); the zero entries of both factors only add exact zeros. */
+static inline void rel_scaled(const orc_ctx *ctx, double px, double py, double t, double *ux, double *uy) {
+  double xt[3];
+  traj_pos(&ctx->traj, t, xt);
+  double yaw = xt[2];
+  double s, c, i00, i11;
+  trig_sincos(ctx, yaw, &s, &c);
+  scale_inv(ctx, t, &i00, &i11);
+  double dx = px - xt[0], dy = py - xt[1];
+  *ux = (c * i00) * dx + (s * i11) * dy;
+  *uy = ((-s) * i00) * dx + (c * i11) * dy;
+}
+
 /* getSDFAtTimeStamp<false> SWM:741-750 = getStateOnTrajStamp SWM:465-474 + posEva2Rel SWM:521-526.
  * Rt = AngleAxisd(yaw, Z) = [[c,-s,0],[s,c,0],[0,0,1]]; p_rel = Rt^T (p - xt). */
-static inline double sdf_at_time(const orc_ctx *ctx, double px, double py, double t) {
+static inline double sdf_at_time_rigid(const orc_ctx *ctx, double px, double py, double t) {
   double xt[3];
   traj_pos(&ctx->traj, t, xt);
   double yaw = xt[2];
@@ -649,8 +686,33 @@ static inline double sdf_at_time(const orc_ctx *ctx, double px, double py, doubl
   tl_cnt.sdf_evals++;
   return orc_shape_sdf(&ctx->shape, rx, ry);
 }
+/* getSDFAtTimeStamp<useScale> SWM:741-750: what the descent and its finite difference evaluate */
+static inline double sdf_at_time(const orc_ctx *ctx, double px, double py, double t) {
+  if (!ctx->use_scale) return sdf_at_time_rigid(ctx, px, py, t);
+  double ux, uy;
+  rel_scaled(ctx, px, py, t, &ux, &uy);
+  tl_cnt.sdf_evals++;
+  return orc_shape_sdf(&ctx->shape, ux, uy);
+}
 double orc_sdf_at_time(orc_ctx *ctx, double px, double py, double t) {
   return sdf_at_time(ctx, px, py, t);
+}
+/* The unit of work with its intermediate: out = (sdf, u_x, u_y), u the body-frame point of getSDFAtTimeStamp under the
+ * context's schedule (the rigid p_rel without one) and modes.  Test convenience only. */
+void orc_rel_at_time(orc_ctx *ctx, double px, double py, double t, double out[3]) {
+  double ux, uy;
+  if (ctx->use_scale) rel_scaled(ctx, px, py, t, &ux, &uy);
+  else {
+    double xt[3], s, c;
+    traj_pos(&ctx->traj, t, xt);
+    trig_sincos(ctx, xt[2], &s, &c);
+    double dx = px - xt[0], dy = py - xt[1];
+    ux = c * dx + s * dy;
+    uy = (-s) * dx + c * dy;
+  }
+  out[0] = orc_shape_sdf(&ctx->shape, ux, uy);
+  out[1] = ux;
+  out[2] = uy;
 }
 
 /* Batch of raw body-frame shape evaluations: getonlySDF(pos_rel) and getonlyGrad1(pos_rel) of the context's shape
@@ -662,9 +724,15 @@ void orc_shape_eval_batch(orc_ctx *ctx, const double *xy, size_t P, double *sdf_
   }
 }
 
-/* getGradPrelAtTimeStamp<false> SWM:779-788 */
+/* getGradPrelAtTimeStamp<useScale> SWM:779-797: getonlyGrad1 at the scaled u under a schedule */
 static inline void grad_prel_at_time(const orc_ctx *ctx, double px, double py, double t,
                                      double g[2]) {
+  if (ctx->use_scale) {
+    double ux, uy;
+    rel_scaled(ctx, px, py, t, &ux, &uy);
+    orc_shape_grad(&ctx->shape, ux, uy, g);
+    return;
+  }
   double xt[3];
   traj_pos(&ctx->traj, t, xt);
   double yaw = xt[2];
@@ -676,7 +744,7 @@ static inline void grad_prel_at_time(const orc_ctx *ctx, double px, double py, d
   orc_shape_grad(&ctx->shape, rx, ry, g);
 }
 
-/* getSDF_DOTAtTimeStamp<false> SWM:799-806 (the analytic form below it is unreachable) */
+/* getSDF_DOTAtTimeStamp<useScale> SWM:799-806 (the analytic form below it, the only reader of getDotScale, is unreachable) */
 static inline double sdf_dot_at_time(const orc_ctx *ctx, double px, double py, double t) {
   double t1 = dmax(0.0, t - 0.000001);
   double t2 = dmin(ctx->traj.traj_duration, t + 0.000001);
@@ -685,7 +753,8 @@ static inline double sdf_dot_at_time(const orc_ctx *ctx, double px, double py, d
   return (sdf2 - sdf1) * 500000;
 }
 
-/* choiceTInit<false>(pos_eva, dt) SWM:538-581 */
+/* choiceTInit<withscale>(pos_eva, dt) SWM:538-581: rigid with the switch on too -- its scan calls the non-scale overload
+ * of getSDFAtTimeStamp (SWM:567-570) */
 static double choice_t_init(const orc_ctx *ctx, double px, double py, double dt) {
   double min_dis = 1e9, dis = 1e9, time_seed = 0.0;
   int pricision_layers = 4, current_layer = 1;
@@ -698,7 +767,7 @@ static double choice_t_init(const orc_ctx *ctx, double px, double py, double dt)
       loop_terminal = dmin(ctx->traj.traj_duration, time_seed + 10 * dt);
     }
     for (; t <= loop_terminal; t += dt) {
-      dis = sdf_at_time(ctx, px, py, t);
+      dis = sdf_at_time_rigid(ctx, px, py, t);
       if (dis < min_dis) { time_seed = t; min_dis = dis; }
     }
     dt *= 0.1;
@@ -760,7 +829,7 @@ static void gradient_descent(const orc_ctx *ctx, double t_min, double t_max, con
   tl_cnt.gd_pass_hist[passes / 4 < 31 ? passes / 4 : 31]++;
 }
 
-/* getSDFofSweptVolume<false,true> SWM:844-866 */
+/* getSDFofSweptVolume<false,true> SWM:844-866; under a schedule: rigid seed, scaled descent and gradient */
 static double sdf_swept(const orc_ctx *ctx, double px, double py, double *time_seed_f,
                         double grad[3]) {
   double t_star = 0.0, sdf_star = 0.0, dtime = 0.15;
@@ -923,13 +992,24 @@ static void point_contribution(const orc_ctx *ctx, double px, double py, point_c
     double gy = (-sy) * gradp_rel[0] + cy * gradp_rel[1];
     gradp_rel[0] = gx; gradp_rel[1] = gy;
   }
-  /* grad_cost_p_sw BEO:1031-1066 (St = I) */
+  /* grad_cost_p_sw BEO:1031-1066 (St = I without a schedule) */
   double costp = 0.0, gradp[2] = {0, 0}, grad_yaw = 0.0;
   double sdf_cost = -1.0, sdf_out_grad = 0.0;
   orc_smoothed_l1(ctx->safety_hor - sdf_value, 0.01, &sdf_cost, &sdf_out_grad);
-  /* sdf_grad = -L' * ( -(St^-1)^T * rotate * gradp_rel ) */
-  double mrx = (-cy) * gradp_rel[0] + (sy) * gradp_rel[1];
-  double mry = (-sy) * gradp_rel[0] + (-cy) * gradp_rel[1];
+  /* sdf_grad = -L' * ( -(St^-1)^T * rotate * gradp_rel ) (BEO:1050) */
+  double mrx, mry;
+  if (ctx->use_scale) {
+    /* St = getScale(time_seed_f), time_seed_f = t* (BEO:795, 827); (-(St^-1)^T) * rotate is formed as a matrix first:
+     * [[(-i00) c, (-i00)(-s)], [(-i11) s, (-i11) c]] (the zero entries add exact zeros).  The yaw term below keeps the rigid
+     * gradp_rel^T (VR_theta^T p_minus_x) with no St^-1, as the reference has it (BEO:1062). */
+    double i00, i11;
+    scale_inv(ctx, time_star, &i00, &i11);
+    mrx = ((-i00) * cy) * gradp_rel[0] + ((-i00) * (-sy)) * gradp_rel[1];
+    mry = ((-i11) * sy) * gradp_rel[0] + ((-i11) * cy) * gradp_rel[1];
+  } else {
+    mrx = (-cy) * gradp_rel[0] + (sy) * gradp_rel[1];
+    mry = (-sy) * gradp_rel[0] + (-cy) * gradp_rel[1];
+  }
   double sgx = -sdf_out_grad * mrx, sgy = -sdf_out_grad * mry;
   if (sdf_cost > 0) {
     costp += sdf_cost;
@@ -1075,6 +1155,18 @@ void orc_destroy(orc_ctx *ctx) {
   free(ctx->traj.T);
   free(ctx->traj.c);
   free(ctx);
+}
+
+/* The schedule of getScale (SWM:495-503) for this context; enabled = 0 clears it (useScale = false, the rigid code). */
+void orc_set_scale(orc_ctx *ctx, const double c[2], const double amp[2], const double omega[2], const double phase[2],
+                   int enabled) {
+  ctx->use_scale = enabled ? 1 : 0;
+  for (int a = 0; a < 2; ++a) {
+    ctx->sc_c[a] = enabled ? c[a] : 1.0;
+    ctx->sc_amp[a] = enabled ? amp[a] : 0.0;
+    ctx->sc_omega[a] = enabled ? omega[a] : 0.0;
+    ctx->sc_phase[a] = enabled ? phase[a] : 0.0;
+  }
 }
 
 int orc_set_polygon_loops(orc_ctx *ctx, const int *loop_sizes, int nloops) {

@@ -123,7 +123,18 @@ void orc_set_traj(orc_ctx *ctx, int N, const double *coeffs_colmajor, const doub
 double orc_traj_duration(const orc_ctx *ctx);
 void orc_traj_pos(const orc_ctx *ctx, double t, double out[3]);   /* TRJ:518-522 */
 void orc_traj_vel(const orc_ctx *ctx, double t, double out[3]);   /* TRJ:524-528 */
-double orc_sdf_at_time(orc_ctx *ctx, double px, double py, double t); /* SWM:741-750 */
+double orc_sdf_at_time(orc_ctx *ctx, double px, double py, double t); /* SWM:741-750 (under the schedule, if one is set) */
+/* Time-varying robot scale, the reference's `useScale = true` (SWM:17) with getScale(t) = diag(s_x, s_y, 1),
+ * s_a(t) = c_a + sin(omega_a t + phase_a) amp_a (the form of the schedule in getScale's comment, SWM:495-503).  S(t) enters
+ * where the switch puts it: the descent's evaluations and the gradient take u = (Rt^T S(t)^-1)(p - x(t)) (SWM:528-535,
+ * S^-1 as Eigen's inverse(): cofactors times 1 / det), grad_cost_p_sw the position gradient -(S(t*)^-1)^T R g (BEO:1050);
+ * choiceTInit and the yaw gradient stay rigid (SWM:567-570, BEO:1062).  The sine goes through the context's trig mode.
+ * enabled = 0 clears the schedule: the rigid code runs, with the bits it always had.  orc_query, orc_penalty,
+ * orc_cost_function, orc_sdf_swept and orc_true_sdf honour it. */
+void orc_set_scale(orc_ctx *ctx, const double c[2], const double amp[2], const double omega[2], const double phase[2],
+                   int enabled);
+/* out = (sdf, u_x, u_y) of getSDFAtTimeStamp at (p, t): u the body-frame point under the context's schedule and modes */
+void orc_rel_at_time(orc_ctx *ctx, double px, double py, double t, double out[3]);
 void orc_shape_eval_batch(orc_ctx *ctx, const double *xy, size_t P, double *sdf_out, double *grad_out);
 
 /* getSDFofSweptVolume<false,true> (SWM:844-866): returns sdf*, writes t* and grad. */
