@@ -200,6 +200,15 @@ struct svsdf_ctx {
   std::vector<int> h_fe_flag;
   size_t fe_edges_cap = 0;
 
+  // resident front-end map (svsdf_frontend_set_map): inflated occupancy bitmap, yaw-free table, kt table, geometry;
+  // pinned + device staging of svsdf_astar_successors [parent yaw | parent ij || child yaw | stage]
+  bool fm_set = false;
+  svsdf::FrontMapDev fm{};
+  unsigned long long *d_fm_occ = nullptr, *d_fm_free = nullptr;
+  double *d_fm_kt = nullptr;
+  unsigned char *d_succ = nullptr, *h_succ = nullptr;
+  size_t succ_cap = 0;                        // parents
+
   // profiling
   bool profile = false;  // per-launch HIP events (env SVSDF_PROFILE=1 or svsdf_set_profiling)
   bool profile_span = false;     // svsdf_set_profiling(ctx, 3): device_ms only -- the span between the evaluation's first and last event, no per-launch events

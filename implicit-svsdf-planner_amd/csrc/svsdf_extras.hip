@@ -10,6 +10,25 @@
 using namespace svsdf;
 using namespace svsdf_impl;
 
+// yaw table of the byte kernels: for (yaw = -PI; yaw < PI; yaw += yaw_res) (SHP:400-401); PI macro of SHP:31
+static std::vector<double> shape_kernel_yaws(int kernel_count, int *loop_count) {
+  const double PI_ = 3.14159265358979323846;
+  const double yaw_res = 2 * PI_ / kernel_count;
+  std::vector<double> yaws;
+  int ind = 0;
+  for (double yaw = -PI_; yaw < PI_; yaw += yaw_res, ind++)
+    if (ind < kernel_count) yaws.push_back(yaw);
+  if (loop_count) *loop_count = ind;
+  return yaws;
+}
+
+// kt = 0, 0.02, ... by accumulated adds while kt <= 1.0 (SWM:1189)
+static int subsw_kt_table(double kt_tab[kMaxKt]) {
+  int nkt = 0;
+  for (double kt = 0.0; kt <= 1.0 && nkt < kMaxKt; kt += 0.02) kt_tab[nkt++] = kt;
+  return nkt;
+}
+
 extern "C" {
 
 // ---- front end -----------------------------------------------------------------
@@ -35,10 +54,8 @@ int svsdf_check_sub_sw_collision(svsdf_ctx *ctx, size_t n_edges, const double *f
   }
   if (n_edges > 0x7fffffffu || (max_pts + kSubswPoints - 1) / kSubswPoints > 65535u)
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_check_sub_sw_collision: batch too large");
-  // kt = 0, 0.02, ... by accumulated adds while kt <= 1.0 (SWM:1189)
   double kt_tab[kMaxKt];
-  int nkt = 0;
-  for (double kt = 0.0; kt <= 1.0 && nkt < kMaxKt; kt += 0.02) kt_tab[nkt++] = kt;
+  const int nkt = subsw_kt_table(kt_tab);
   if (total == 0) { std::memset(free_out, 1, n_edges); return SVSDF_OK; }
   HIPCHK(hipSetDevice(ctx->device));
   // one packed upload: [father 3E | child 3E | kt 64 | offsets E+1 (u64) | pts 2T] through a pinned staging buffer
@@ -94,13 +111,8 @@ int svsdf_shape_kernels(svsdf_ctx *ctx, int kernel_size, int kernel_count, doubl
   if (ctx->cfg.shape_id == SVSDF_SHAPE_Polygon)
     return fail(ctx, SVSDF_ERR_INVALID,
                 "svsdf_shape_kernels: Polygon has no getonlySDF(pos_rel, Matrix3d) in the reference (Shape.hpp:1477)");
-  // yaw table: for (yaw = -PI; yaw < PI; yaw += yaw_res) (SHP:400-401); PI macro of SHP:31
-  const double PI_ = 3.14159265358979323846;
-  const double yaw_res = 2 * PI_ / kernel_count;
-  std::vector<double> yaws;
   int ind = 0;
-  for (double yaw = -PI_; yaw < PI_; yaw += yaw_res, ind++)
-    if (ind < kernel_count) yaws.push_back(yaw);
+  const std::vector<double> yaws = shape_kernel_yaws(kernel_count, &ind);
   if (loop_count) *loop_count = ind;
   const int count = (int)yaws.size();
   const int size_side = (int)(0.5 * (kernel_size - 1));
@@ -180,6 +192,185 @@ int svsdf_pcd_read_ascii(const char *path, float *xyz, size_t capacity, size_t *
   if (xyz) {
     if (capacity < *n) return SVSDF_ERR_INVALID;
     std::copy(v.begin(), v.end(), xyz);
+  }
+  return SVSDF_OK;
+}
+
+// ---- front end: resident map, yaw-free table, batched successor test ---------------------------------------------
+static void frontend_release(svsdf_ctx *ctx) {
+  ctx->fm_set = false;
+  for (void *p : {(void *)ctx->d_fm_occ, (void *)ctx->d_fm_free, (void *)ctx->d_fm_kt})
+    if (p) (void)hipFree(p);
+  ctx->d_fm_occ = ctx->d_fm_free = nullptr;
+  ctx->d_fm_kt = nullptr;
+}
+
+int svsdf_frontend_set_map(svsdf_ctx *ctx, const svsdf_map *map, int kernel_size, int kernel_count, double safemargin) {
+  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_frontend_set_map: no device context");
+  if (!ctx->subs.empty()) {
+    const int r = svsdf_frontend_set_map(ctx->subs[0], map, kernel_size, kernel_count, safemargin);
+    if (r) ctx->err = ctx->subs[0]->err;
+    return r;
+  }
+  if (!map) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: null map");
+  if (ctx->cfg.shape_id == SVSDF_SHAPE_Polygon)
+    return fail(ctx, SVSDF_ERR_INVALID,
+                "svsdf_frontend_set_map: Polygon has no getonlySDF(pos_rel, Matrix3d) in the reference (Shape.hpp:1477), so no yaw kernels");
+  if (kernel_size <= 0 || kernel_size % 2 == 0)
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: kernel_size must be odd and positive");
+  if (kernel_size > kMaxKernelSize || kernel_count > kMaxKernelCount || kernel_count < 1)
+    return fail(ctx, SVSDF_ERR_INVALID,
+                "svsdf_frontend_set_map: kernel_size <= 63 and 1 <= kernel_count <= 64 (a kernel row and a cell's mask are one word each)");
+  if (!std::isfinite(safemargin)) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: safemargin not finite");
+  const svsdf_host::OccupancyMap &m = map->m;
+  const int X = m.dims()[0], Y = m.dims()[1], Z = m.dims()[2];
+  const int side = (kernel_size - 1) / 2;
+  if (X < 1 || Y < 1 || Z < 1) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: empty map");
+  if ((Y + kYawFreeBlock - 1) / kYawFreeBlock > 65535 || (long long)X * Y > 0x7fffffffll)
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: map too large");
+  int loops = 0;
+  const std::vector<double> yaws = shape_kernel_yaws(kernel_count, &loops);
+  if ((int)yaws.size() != kernel_count)
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: the reference's yaw loop yields fewer kernels than kernel_count");
+  // generateMapKernel2D (PCSmap_manager.h:81-108) in 64-bit row words: layer iz = 0, cell (x, y) at (x + side, y + side)
+  const int row_words = (Y + 2 * side + 63) / 64 + 1;
+  const size_t rows = (size_t)X + 2 * (size_t)side;
+  std::vector<unsigned long long> occ(rows * row_words, 0ull);
+  for (int x = 0; x < X; ++x)
+    for (int y = 0; y < Y; ++y)
+      if (m.cell(x, y, 0)) occ[(size_t)(x + side) * row_words + ((y + side) >> 6)] |= 1ull << ((y + side) & 63);
+  double kt_tab[kMaxKt];
+  const int nkt = subsw_kt_table(kt_tab);
+
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  frontend_release(ctx);
+  const size_t cells = (size_t)kernel_size * kernel_size;
+  double *d_yaw = nullptr;
+  unsigned char *d_bytes = nullptr;
+  unsigned long long *d_krows = nullptr;
+  hipStream_t st = ctx->stream;
+  hipError_t err = hipSuccess;
+  bool compiled = true;
+  auto ok = [&](hipError_t e) { if (err == hipSuccess) err = e; return err == hipSuccess; };
+  if (ok(hipMalloc((void **)&d_yaw, kernel_count * sizeof(double))) && ok(hipMalloc((void **)&d_bytes, cells * kernel_count)) &&
+      ok(hipMalloc((void **)&d_krows, (size_t)kernel_size * kernel_count * sizeof(unsigned long long))) &&
+      ok(hipMalloc((void **)&ctx->d_fm_occ, occ.size() * sizeof(unsigned long long))) &&
+      ok(hipMalloc((void **)&ctx->d_fm_free, (size_t)X * Y * sizeof(unsigned long long))) &&
+      ok(hipMalloc((void **)&ctx->d_fm_kt, kMaxKt * sizeof(double))) &&
+      ok(hipMemcpyAsync(d_yaw, yaws.data(), kernel_count * sizeof(double), hipMemcpyHostToDevice, st)) &&
+      ok(hipMemcpyAsync(ctx->d_fm_occ, occ.data(), occ.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st)) &&
+      ok(hipMemcpyAsync(ctx->d_fm_kt, kt_tab, kMaxKt * sizeof(double), hipMemcpyHostToDevice, st))) {
+    // the kernel resolution is the map's: kernelConv overlays kernel cells on map cells one to one
+    const unsigned grid = (unsigned)((cells * kernel_count + kBlock - 1) / kBlock);
+    compiled = launch_k_shape_kernels(ctx->cfg.shape_id, grid, st, ctx->sp, kernel_size, kernel_count, m.resolution(), side,
+                                      safemargin, d_yaw, d_bytes);
+    if (compiled && ok(hipGetLastError())) {
+      launch_k_pack_kernel_rows(st, d_bytes, kernel_size, kernel_count, d_krows);
+      if (ok(hipGetLastError())) {
+        launch_k_yaw_free(st, ctx->d_fm_occ, row_words, d_krows, kernel_size, kernel_count, X, Y, ctx->d_fm_free);
+        ok(hipGetLastError());
+      }
+    }
+  }
+  ok(hipStreamSynchronize(st));   // (also before the pageable sources above go out of scope)
+  for (void *p : {(void *)d_yaw, (void *)d_bytes, (void *)d_krows})
+    if (p) (void)hipFree(p);
+  if (err != hipSuccess || !compiled) {
+    frontend_release(ctx);
+    if (!compiled) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: shape not compiled into this library");
+    return fail(ctx, SVSDF_ERR_HIP_BASE + (int)err, std::string("svsdf_frontend_set_map: ") + hipGetErrorString(err));
+  }
+  FrontMapDev &fm = ctx->fm;
+  fm.occ = ctx->d_fm_occ; fm.free_ = ctx->d_fm_free; fm.kt = ctx->d_fm_kt; fm.nkt = nkt;
+  fm.X = X; fm.Y = Y; fm.side = side; fm.row_words = row_words; fm.kernel_count = kernel_count;
+  fm.res = m.resolution();
+  fm.half = (double)(kernel_size / 2 + 1);   // front_end_Astar.hpp:224: integer division, metres
+  for (int d = 0; d < 3; ++d) { fm.bmin[d] = m.bmin()[d]; fm.bmax[d] = m.bmax()[d]; }
+  ctx->fm_set = true;
+  return SVSDF_OK;
+}
+
+int svsdf_frontend_yaw_free(const svsdf_ctx *cctx, unsigned long long *mask_out, size_t capacity, int dims2[2]) {
+  svsdf_ctx *ctx = const_cast<svsdf_ctx *>(cctx);   // (the error string is the only thing written)
+  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_frontend_yaw_free: no device context");
+  if (!ctx->subs.empty()) {
+    const int r = svsdf_frontend_yaw_free(ctx->subs[0], mask_out, capacity, dims2);
+    if (r) ctx->err = ctx->subs[0]->err;
+    return r;
+  }
+  if (!ctx->fm_set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_yaw_free: no map (svsdf_frontend_set_map)");
+  if (dims2) { dims2[0] = ctx->fm.X; dims2[1] = ctx->fm.Y; }
+  if (!mask_out) return SVSDF_OK;
+  const size_t n = (size_t)ctx->fm.X * ctx->fm.Y;
+  if (capacity < n) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_yaw_free: capacity too small (query with mask_out = NULL first)");
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipMemcpyAsync(mask_out, ctx->d_fm_free, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return SVSDF_OK;
+}
+
+int svsdf_kernel_bfs(unsigned long long free_mask, int kernel_count, double father_yaw, double *child_yaw, int *kernel_index) {
+  if (!child_yaw || !kernel_index) return -3;
+  return kernel_bfs(free_mask, kernel_count, father_yaw, child_yaw, kernel_index);
+}
+
+int svsdf_astar_successors(svsdf_ctx *ctx, size_t n, const int *parent_ij, const double *parent_yaw, unsigned char *ok_out,
+                           double *child_yaw_out, unsigned char *stage_out) {
+  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_astar_successors: no device context");
+  if (!ctx->subs.empty()) {
+    const int r = svsdf_astar_successors(ctx->subs[0], n, parent_ij, parent_yaw, ok_out, child_yaw_out, stage_out);
+    if (r) ctx->err = ctx->subs[0]->err;
+    return r;
+  }
+  if (!ctx->fm_set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: no map (svsdf_frontend_set_map)");
+  if (n == 0) return SVSDF_OK;
+  if (!parent_ij || !parent_yaw || !ok_out || !child_yaw_out)
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: null argument");
+  const FrontMapDev &fm = ctx->fm;
+  for (size_t p = 0; p < n; ++p) {
+    const int i = parent_ij[2 * p], j = parent_ij[2 * p + 1];
+    if (i < 0 || i >= fm.X || j < 0 || j >= fm.Y)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: parent " + std::to_string(p) + " is outside the map");
+    double cy;
+    int ki;
+    if (kernel_bfs(0ull, fm.kernel_count, parent_yaw[p], &cy, &ki) < 0)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: yaw of parent " + std::to_string(p) +
+                                              " maps to a kernel index outside [0, kernel_count)");
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  constexpr size_t kSuccParents = (size_t)1 << 18;       // parents per launch: 9 blocks each, well inside one grid dimension
+  constexpr size_t kIn = 16, kOut = 81;            // bytes per parent: yaw + ij | 9 child yaws + 9 stages
+  const size_t want = std::min(n, kSuccParents);
+  if (want > ctx->succ_cap) {
+    const size_t cap = std::min(kSuccParents, want + want / 2);
+    int rc = dev_alloc(ctx, &ctx->d_succ, cap * (kIn + kOut));
+    if (rc) return rc;
+    ctx->succ_cap = 0;
+    if (ctx->h_succ) { (void)hipHostFree(ctx->h_succ); ctx->h_succ = nullptr; }
+    HIPCHK(hipHostMalloc((void **)&ctx->h_succ, cap * (kIn + kOut)));
+    ctx->succ_cap = cap;
+  }
+  hipStream_t st = ctx->stream;
+  for (size_t p0 = 0; p0 < n; p0 += kSuccParents) {
+    const size_t m = std::min(kSuccParents, n - p0);
+    // one upload [yaw m (f64) | ij 2m (i32)], one read-back [child yaw 9m (f64) | stage 9m (u8)]
+    unsigned char *h = ctx->h_succ, *d = ctx->d_succ;
+    std::memcpy(h, parent_yaw + p0, m * sizeof(double));
+    std::memcpy(h + 8 * m, parent_ij + 2 * p0, 2 * m * sizeof(int));
+    HIPCHK(hipMemcpyAsync(d, h, kIn * m, hipMemcpyHostToDevice, st));
+    double *d_yaw_out = reinterpret_cast<double *>(d + kIn * m);
+    unsigned char *d_stage = d + kIn * m + 72 * m;
+    if (!launch_k_succ(ctx->cfg.shape_id, (unsigned)(9 * m), st, ctx->sp, fm, reinterpret_cast<const int *>(d + 8 * m),
+                       reinterpret_cast<const double *>(d), d_yaw_out, d_stage))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: shape not compiled into this library");
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h + kIn * m, d + kIn * m, kOut * m, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::memcpy(child_yaw_out + 9 * p0, h + kIn * m, 72 * m);
+    const unsigned char *hs = h + kIn * m + 72 * m;
+    for (size_t e = 0; e < 9 * m; ++e) ok_out[9 * p0 + e] = hs[e] == 0 ? 1 : 0;
+    if (stage_out) std::memcpy(stage_out + 9 * p0, hs, 9 * m);
   }
   return SVSDF_OK;
 }

@@ -2,6 +2,9 @@
 //
 //   k_subsw<SHAPE>         SweptVolumeManager::checkSubSWCollision (SWM:1171-1211), batched over A* edges
 //   k_shape_kernels<SHAPE> BasicShape::initShape (SHP:386-430): occupancy of the kernel cells per yaw
+//   k_yaw_free             kernelConv<true> (SWM:1033-1099) for every (cell, yaw kernel) of a map: the yaw-free table
+//   kernel_bfs             checkKernelValue + visit_kernels_by_distance (SWM:1103-1169) on one cell's table word
+//   k_succ<SHAPE>          the successor test of AstarPathSearcher::AstarGetSucc (front_end_Astar.hpp:192-241), batched
 //
 // Both are maps over independent (edge, obstacle point, interpolation step) / (yaw, cell) items with a
 // boolean reduction; the reference's early exits only shorten its loops, they never change the result, so
@@ -80,6 +83,229 @@ k_shape_kernels(ShapeParams sp, int ks, int count, double resu, int size_side, d
   } else {
     map[gid] = (shape_sdf_rot<SHAPE>(sp, x, y, cs, sn) <= safemargin) ? 1 : 0;
   }
+}
+
+// ---- yaw-kernel free-space table and batched A* successor test -------------------------------------------------------
+//
+// Bit layout shared by the packed map and the packed kernels: bit (y & 63) of word (y >> 6) of a row.  A map row is one
+// row (fixed x) of the reference's INFLATED map (generateMapKernel2D, PCSmap_manager.h:81-108): (X + 2 side) rows of
+// (Y + 2 side) bits, cell (x, y) at (x + side, y + side), zero outside the map, padded to `row_words` words so that the
+// word after any cell's word exists.  A kernel row is row a of byte kernel k: bit b = kernels[k][a][b], zero from
+// kernel_size on.  kernelConv<true>(k, (ix, iy, 0)) ANDs kernel row a with the bits [iy, iy + 8 bpl) of inflated row
+// ix + a; the bits it reads past a row (or past the array) only meet kernel columns >= kernel_size, which are zero, so
+// the test is `window(ix + a, iy) & kernel_row(k, a)` over kernel_size columns.
+constexpr int kMaxKernelSize = 63;    // a kernel row is one word
+constexpr int kMaxKernelCount = 64;   // a cell's mask is one word
+constexpr int kYawFreeBlock = 256;    // 4 waves: 256 consecutive iy of one ix
+constexpr int kYawFreeRowWords = kYawFreeBlock / 64 + 1;
+constexpr int kSuccBlock = 256;
+constexpr int kSuccPoints = 1024;     // obstacle cells a block of k_succ holds in LDS before it evaluates them
+
+// Resident front-end map as the kernels see it (svsdf_frontend_set_map).
+struct FrontMapDev {
+  const unsigned long long *occ;    // inflated bitmap, (X + 2 side) x row_words
+  const unsigned long long *free_;  // yaw-free table [ix * Y + iy]
+  const double *kt;                 // the 50 accumulated interpolation steps of SWM:1189
+  int nkt;
+  int X, Y, side, row_words, kernel_count;
+  double res, half;                 // cell size; half extent of getPointsInAABB2D: kernel_size / 2 + 1, in metres
+  double bmin[3], bmax[3];
+};
+
+// checkKernelValue (SWM:1158-1169) + visit_kernels_by_distance (:1103-1156) on one cell's word of the yaw-free table.
+// Returns 1 and writes both outputs when a kernel is found, 0 when none (outputs untouched), -1 when the father's index
+// falls outside [0, kernel_count) (the reference indexes past its arrays there), -2 for a bad kernel_count.
+// `pi` is sw_manager.hpp:20's literal, not the PI of the yaw table (Shape.hpp:31).
+__host__ __device__ inline int kernel_bfs(unsigned long long free_mask, int kernel_count, double father_yaw,
+                                          double *child_yaw, int *kernel_index) {
+  if (kernel_count < 1 || kernel_count > kMaxKernelCount) return -2;
+  const double pi = 3.1415926536;
+  const double v = kernel_count * ((father_yaw + pi) / (2 * pi));
+  if (!(v > -1.0 && v < (double)kernel_count)) return -1;   // (NaN too)
+  const int father_i = (int)v;                               // truncation: (-1, 0) -> 0
+  // the queue of the breadth-first search: at most 11 pops, two pushes each; one byte per entry in three words
+  unsigned long long q0 = (unsigned long long)father_i, q1 = 0ull, q2 = 0ull;
+  unsigned long long visited = 1ull << father_i;
+  int head = 0, tail = 1, deep = 0;
+  while (head < tail) {
+    ++deep;
+    const unsigned long long qw = head < 8 ? q0 : (head < 16 ? q1 : q2);
+    const int x = (int)((qw >> ((head & 7) * 8)) & 0xffull);
+    ++head;
+    if ((free_mask >> x) & 1ull) {
+      *kernel_index = x;
+      *child_yaw = 2 * pi * x / kernel_count - pi;
+      return 1;
+    }
+    for (int dir = -1; dir <= 1; dir += 2) {
+      int nx = x + dir;
+      if (nx < 0) nx = kernel_count - 1;
+      if (nx >= kernel_count) nx = 0;
+      if ((visited >> nx) & 1ull) continue;
+      visited |= 1ull << nx;
+      const unsigned long long e = (unsigned long long)nx << ((tail & 7) * 8);
+      if (tail < 8) q0 |= e; else if (tail < 16) q1 |= e; else q2 |= e;
+      ++tail;
+    }
+    if (deep > 10) break;
+  }
+  return 0;
+}
+
+#ifdef SVSDF_API_TU   // shape-independent kernels: compiled once, by svsdf_pipeline.hip
+// Byte kernels of k_shape_kernels ([k][a][b], one byte per cell) -> one word per (k, a).
+__global__ void __launch_bounds__(kBlock)
+k_pack_kernel_rows(const unsigned char *__restrict__ map, int ks, int count, unsigned long long *__restrict__ rows) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= ks * count) return;
+  const unsigned char *m = map + (size_t)r * ks;
+  unsigned long long w = 0ull;
+  for (int b = 0; b < ks; ++b) w |= (unsigned long long)(m[b] != 0) << b;
+  rows[r] = w;
+}
+
+// One block = 256 consecutive iy (blockIdx.y) of one ix (blockIdx.x), a wave = 64 of them.  LDS: the ks map rows
+// ix .. ix + ks - 1 of the inflated bitmap (the 5 words the block's windows touch) and all kernel rows.  A lane forms
+// its window of row a with a two-word funnel shift and tests it against the wave-uniform kernel words; every lane
+// runs the same ks x count trip, the mask is stored once.
+__global__ void __launch_bounds__(kYawFreeBlock)
+k_yaw_free(const unsigned long long *__restrict__ occ, int row_words, const unsigned long long *__restrict__ krows,
+           int ks, int count, int X, int Y, unsigned long long *__restrict__ free_out) {
+  extern __shared__ unsigned long long yf_lds[];
+  unsigned long long *s_map = yf_lds;                           // [ks][kYawFreeRowWords]
+  unsigned long long *s_k = yf_lds + ks * kYawFreeRowWords;     // [count][ks]
+  const int ix = blockIdx.x;
+  const int w0 = blockIdx.y * (kYawFreeBlock / 64);
+  for (int t = threadIdx.x; t < ks * kYawFreeRowWords; t += kYawFreeBlock) {
+    const int a = t / kYawFreeRowWords, w = t - a * kYawFreeRowWords;
+    s_map[t] = (w0 + w < row_words) ? occ[(size_t)(ix + a) * row_words + (w0 + w)] : 0ull;
+  }
+  for (int t = threadIdx.x; t < ks * count; t += kYawFreeBlock) s_k[t] = krows[t];
+  __syncthreads();
+  const int iy = blockIdx.y * kYawFreeBlock + threadIdx.x;
+  if (iy >= Y) return;
+  const int wq = threadIdx.x >> 6, sh = iy & 63;
+  unsigned long long hit = 0ull;
+  for (int a = 0; a < ks; ++a) {
+    const unsigned long long lo = s_map[a * kYawFreeRowWords + wq], hi = s_map[a * kYawFreeRowWords + wq + 1];
+    const unsigned long long win = sh ? ((lo >> sh) | (hi << (64 - sh))) : lo;
+    for (int k = 0; k < count; ++k)
+      hit |= (unsigned long long)((win & s_k[k * ks + a]) != 0ull) << k;
+  }
+  const unsigned long long all = count >= 64 ? ~0ull : ((1ull << count) - 1ull);
+  free_out[(size_t)ix * Y + iy] = ~hit & all;
+}
+#endif  // SVSDF_API_TU
+
+// getGridIndex (Gridmap3D.cpp:137-177) of a coordinate that projInMap (PCSmap_manager.h:128-135) has clamped into the map
+__device__ __forceinline__ int succ_box_index(double c, double half, double bmin, double bmax, double res, int size) {
+  double a = c + half;
+  if (a < bmin) a = bmin;
+  if (a > bmax) a = bmax;
+  int i = (int)floor((a - bmin) / res);
+  if (i < 0) i = 0;
+  if (i >= size) i = size - 1;
+  return i;
+}
+
+// One block = one (parent, neighbour): e = 9 p + 3 (i + 1) + (j + 1), the loop order of AstarGetSucc.  Thread 0 runs the
+// cheap stages -- isIndexValid, the cell's own bit (isIndexOccupiedFlate(vi, 0)), kernel_bfs on the cell's table word --
+// and the block goes on only for a child that has a yaw.  It then walks the index box of getPointsInAABB2D
+// (PCSmap_manager.h:137-158) 256 cells at a time, compacts the occupied ones into an LDS list (__ballot + popcount
+// prefix) and deals the (point, step) pairs of checkSubSWCollision over its threads, exactly as k_subsw evaluates them.
+// stage: 0 accepted, 1 index invalid, 2 cell occupied, 3 no yaw kernel, 4 sub-swept-volume collision.
+template <int SHAPE>
+__global__ void __launch_bounds__(kSuccBlock)
+k_succ(ShapeParams sp, FrontMapDev fm, const int *__restrict__ parent_ij, const double *__restrict__ parent_yaw,
+       double *__restrict__ yaw_out, unsigned char *__restrict__ stage_out) {
+  __shared__ double s_x[kMaxKt], s_y[kMaxKt], s_c[kMaxKt], s_s[kMaxKt];
+  __shared__ int s_pi[kSuccPoints], s_pj[kSuccPoints];
+  __shared__ int s_wcnt[kSuccBlock / 64];
+  __shared__ int s_stage;
+  __shared__ double s_cy;
+  const unsigned e = blockIdx.x;
+  const unsigned p = e / 9u, slot = e - 9u * p;
+  const int pi_ = parent_ij[2 * p], pj_ = parent_ij[2 * p + 1];
+  const int vi = pi_ + (int)(slot / 3u) - 1, vj = pj_ + (int)(slot % 3u) - 1;
+  const double fy = parent_yaw[p];
+  if (threadIdx.x == 0) {
+    int stage = 0, ki = 0;
+    double cy = __longlong_as_double(0x7ff8000000000000ll);
+    if (vi < 0 || vi >= fm.X || vj < 0 || vj >= fm.Y) {
+      stage = 1;
+    } else if ((fm.occ[(size_t)(vi + fm.side) * fm.row_words + ((vj + fm.side) >> 6)] >> ((vj + fm.side) & 63)) & 1ull) {
+      stage = 2;
+    } else if (kernel_bfs(fm.free_[(size_t)vi * fm.Y + vj], fm.kernel_count, fy, &cy, &ki) != 1) {
+      stage = 3;
+    }
+    s_stage = stage;
+    s_cy = cy;
+    if (stage) { yaw_out[e] = cy; stage_out[e] = (unsigned char)stage; }
+  }
+  __syncthreads();
+  if (s_stage) return;
+  const double cy = s_cy;
+  // getGridCubeCenter (Gridmap3D.cpp:184-195)
+  const double fx = (pi_ + 0.5) * fm.res + fm.bmin[0], fyy = (pj_ + 0.5) * fm.res + fm.bmin[1];
+  const double cx = (vi + 0.5) * fm.res + fm.bmin[0], cyy = (vj + 0.5) * fm.res + fm.bmin[1];
+  if (threadIdx.x < (unsigned)fm.nkt) {
+    const double kt = fm.kt[threadIdx.x];
+    const double omk = 1 - kt;
+    const double lx = kt * cx + omk * fx;
+    const double ly = kt * cyy + omk * fyy;
+    const double yaw = kt * cy + omk * fy;
+    double sn, cs;
+    sincos_exact(yaw, &sn, &cs);
+    s_x[threadIdx.x] = lx; s_y[threadIdx.x] = ly; s_c[threadIdx.x] = cs; s_s[threadIdx.x] = sn;
+  }
+  const int i1 = succ_box_index(cx, -fm.half, fm.bmin[0], fm.bmax[0], fm.res, fm.X);
+  const int i2 = succ_box_index(cx, fm.half, fm.bmin[0], fm.bmax[0], fm.res, fm.X);
+  const int j1 = succ_box_index(cyy, -fm.half, fm.bmin[1], fm.bmax[1], fm.res, fm.Y);
+  const int j2 = succ_box_index(cyy, fm.half, fm.bmin[1], fm.bmax[1], fm.res, fm.Y);
+  const unsigned bh = (unsigned)(j2 - j1 + 1);
+  const unsigned long long total = (i2 >= i1 && j2 >= j1) ? (unsigned long long)(i2 - i1 + 1) * bh : 0ull;
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  int n = 0;          // points in the list: every thread keeps the same count
+  bool hit = false;
+  for (unsigned long long base = 0; base < total; base += kSuccBlock) {
+    const unsigned long long c = base + threadIdx.x;
+    bool occ = false;
+    int ci = 0, cj = 0;
+    if (c < total) {
+      ci = i1 + (int)(c / bh);
+      cj = j1 + (int)(c % bh);
+      occ = (fm.occ[(size_t)(ci + fm.side) * fm.row_words + ((cj + fm.side) >> 6)] >> ((cj + fm.side) & 63)) & 1ull;
+    }
+    const unsigned long long bal = __ballot(occ);
+    if (lane == 0) s_wcnt[wave] = __popcll(bal);
+    __syncthreads();   // (also: the poses are written, the previous flush has read the list)
+    int off = n, add = 0;
+    for (unsigned w = 0; w < kSuccBlock / 64; ++w) {
+      if (w < wave) off += s_wcnt[w];
+      add += s_wcnt[w];
+    }
+    if (occ) {
+      const int at = off + __popcll(bal & ((1ull << lane) - 1ull));
+      s_pi[at] = ci; s_pj[at] = cj;
+    }
+    n += add;
+    __syncthreads();
+    if (n > kSuccPoints - kSuccBlock || base + kSuccBlock >= total) {
+      const unsigned pairs = (unsigned)n * (unsigned)fm.nkt;
+      for (unsigned q = threadIdx.x; q < pairs && !hit; q += kSuccBlock) {
+        const unsigned ip = q / (unsigned)fm.nkt, k = q - ip * (unsigned)fm.nkt;
+        const double px = (s_pi[ip] + 0.5) * fm.res + fm.bmin[0], py = (s_pj[ip] + 0.5) * fm.res + fm.bmin[1];
+        const double dx = px - s_x[k], dy = py - s_y[k];
+        const double c_ = s_c[k], s_ = s_s[k];
+        const double rx = c_ * dx + s_ * dy;       // posEva2Rel: Rt^T (p - x)  SWM:521-526
+        const double ry = (-s_) * dx + c_ * dy;
+        if (shape_sdf<SHAPE>(sp, rx, ry) < 0) hit = true;
+      }
+      n = 0;
+      if (__syncthreads_or(hit)) { hit = true; break; }   // a pure AND: a found collision ends the edge
+    }
+  }
+  if (threadIdx.x == 0) { yaw_out[e] = cy; stage_out[e] = hit ? 4 : 0; }
 }
 
 // Diagnostic / test kernel (svsdf_debug_sdf_at): getSDFAtTimeStamp<false> (SWM:741-750) for arbitrary (point, time) pairs

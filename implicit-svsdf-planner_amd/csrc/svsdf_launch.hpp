@@ -52,6 +52,12 @@ bool launch_k_shape_kernels(int shape, unsigned grid, hipStream_t st, ShapeParam
                             int size_side, double safemargin, const double *yaw, unsigned char *map);
 bool launch_k_debug_sdf_at(int shape, unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp,
                            const double *pxy, const double *t, int n, double *out, const ScaleDev *scl = nullptr);
+bool launch_k_succ(int shape, unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const int *parent_ij,
+                   const double *parent_yaw, double *yaw_out, unsigned char *stage_out);
+// shape-independent front-end kernels (svsdf_pipeline.hip)
+void launch_k_pack_kernel_rows(hipStream_t st, const unsigned char *map, int ks, int count, unsigned long long *rows);
+void launch_k_yaw_free(hipStream_t st, const unsigned long long *occ, int row_words, const unsigned long long *krows, int ks,
+                       int count, int X, int Y, unsigned long long *free_out);
 
 // per-slice entry points (defined by svsdf_shape_slice.hip, one set per slice)
 #define SVSDF_DECLARE_SLICE(K)                                                                                              \
@@ -65,7 +71,9 @@ bool launch_k_debug_sdf_at(int shape, unsigned grid, size_t lds, hipStream_t st,
   bool launch_k_shape_kernels_s##K(int shape, unsigned grid, hipStream_t st, ShapeParams sp, int ks, int count, double resu,   \
                                    int size_side, double safemargin, const double *yaw, unsigned char *map);                   \
   bool launch_k_debug_sdf_at_s##K(int shape, unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp,    \
-                                  const double *pxy, const double *t, int n, double *out, const ScaleDev *scl);
+                                  const double *pxy, const double *t, int n, double *out, const ScaleDev *scl);                 \
+  bool launch_k_succ_s##K(int shape, unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm,                      \
+                          const int *parent_ij, const double *parent_yaw, double *yaw_out, unsigned char *stage_out);
 SVSDF_DECLARE_SLICE(0)
 SVSDF_DECLARE_SLICE(1)
 SVSDF_DECLARE_SLICE(2)

@@ -160,6 +160,21 @@ bool launch_k_shape_kernels(int shape, unsigned grid, hipStream_t st, ShapeParam
   shape = svsdf_impl::compiled_shape(shape);
   SVSDF_SLICE_DISPATCH(launch_k_shape_kernels, grid, st, sp, ks, count, resu, size_side, safemargin, yaw, map)
 }
+bool launch_k_succ(int shape, unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const int *parent_ij,
+                   const double *parent_yaw, double *yaw_out, unsigned char *stage_out) {
+  shape = svsdf_impl::compiled_shape(shape);
+  SVSDF_SLICE_DISPATCH(launch_k_succ, grid, st, sp, fm, parent_ij, parent_yaw, yaw_out, stage_out)
+}
+void launch_k_pack_kernel_rows(hipStream_t st, const unsigned char *map, int ks, int count, unsigned long long *rows) {
+  hipLaunchKernelGGL(k_pack_kernel_rows, dim3((unsigned)((ks * count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, map, ks,
+                     count, rows);
+}
+void launch_k_yaw_free(hipStream_t st, const unsigned long long *occ, int row_words, const unsigned long long *krows, int ks,
+                       int count, int X, int Y, unsigned long long *free_out) {
+  const size_t lds = ((size_t)ks * kYawFreeRowWords + (size_t)ks * count) * sizeof(unsigned long long);
+  hipLaunchKernelGGL(k_yaw_free, dim3((unsigned)X, (unsigned)((Y + kYawFreeBlock - 1) / kYawFreeBlock)), dim3(kYawFreeBlock),
+                     lds, st, occ, row_words, krows, ks, count, X, Y, free_out);
+}
 }  // namespace svsdf
 namespace svsdf_impl {
 

@@ -85,6 +85,9 @@ class OccupancyMap {
   const double *bmin() const { return bmin_; }
   const double *bmax() const { return bmax_; }
   size_t occupied_count() const { return occupied_; }
+  double resolution() const { return res_; }
+  // grid_map[toAddr(i, j, k)] of a valid index (the front end packs layer k = 0 into its bitmap)
+  bool cell(int i, int j, int k) const { return occ_[addr(i, j, k)] != 0; }
 
  private:
   bool in_map(double x, double y, double z) const {  // GRD:43-71

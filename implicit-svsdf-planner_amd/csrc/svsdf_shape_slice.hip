@@ -1,6 +1,6 @@
 // svsdf_shape_slice.hip -- one slice of the shape-templated kernels (compile with -DSVSDF_SLICE=k, k = 0 .. 3).
 //
-// Slice k instantiates k_solve / k_round / k_classify / k_rbound / k_subsw / k_shape_kernels for the shapes with
+// Slice k instantiates k_solve / k_round / k_classify / k_rbound / k_subsw / k_shape_kernels / k_succ for the shapes with
 // id % 4 == k and exports the launchers svsdf_pipeline.hip dispatches to (svsdf_launch.hpp).  Splitting the ~250 kernel
 // instantiations over four translation units lets the build run in parallel (one TU took 140 s).
 #include <hip/hip_runtime.h>
@@ -153,6 +153,17 @@ bool shape_kernels_s(unsigned grid, hipStream_t st, ShapeParams sp, int ks, int 
 }
 
 template <int S>
+bool succ_s(unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const int *parent_ij, const double *parent_yaw,
+            double *yaw_out, unsigned char *stage_out) {
+  if constexpr (!shape_enabled<S>() || is_polygon<S>()) {   // no yaw kernels for the Polygon (shape_kernels_s)
+    return false;
+  } else {
+    hipLaunchKernelGGL((k_succ<S>), dim3(grid), dim3(kSuccBlock), 0, st, sp, fm, parent_ij, parent_yaw, yaw_out, stage_out);
+    return true;
+  }
+}
+
+template <int S>
 bool debug_sdf_at_s(unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp, const double *pxy,
                     const double *t, int n, double *out, const ScaleDev *scl) {
   if constexpr (!shape_enabled<S>()) {
@@ -216,6 +227,12 @@ bool SLICE_FN(launch_k_debug_sdf_at)(int shape, unsigned grid, size_t lds, hipSt
 bool SLICE_FN(launch_k_shape_kernels)(int shape, unsigned grid, hipStream_t st, ShapeParams sp, int ks, int count, double resu,
                                       int size_side, double safemargin, const double *yaw, unsigned char *map) {
 #define CALL(S) shape_kernels_s<S>(grid, st, sp, ks, count, resu, size_side, safemargin, yaw, map)
+  SLICE_SWITCH(CALL)
+#undef CALL
+}
+bool SLICE_FN(launch_k_succ)(int shape, unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const int *parent_ij,
+                             const double *parent_yaw, double *yaw_out, unsigned char *stage_out) {
+#define CALL(S) succ_s<S>(grid, st, sp, fm, parent_ij, parent_yaw, yaw_out, stage_out)
   SLICE_SWITCH(CALL)
 #undef CALL
 }

@@ -32,6 +32,7 @@ EXPORTS = [
     "svsdf_get_plan", "svsdf_set_plan", "svsdf_set_combine", "svsdf_group_info", "svsdf_debug_sdf_at",
     "svsdf_group_stripe", "svsdf_set_group_serial", "svsdf_shape_selfcheck", "svsdf_mesh_section", "svsdf_mesh_section_obj",
     "svsdf_last_launches", "svsdf_set_scale", "svsdf_get_scale",
+    "svsdf_frontend_set_map", "svsdf_frontend_yaw_free", "svsdf_kernel_bfs", "svsdf_astar_successors",
 ]
 
 
@@ -191,6 +192,10 @@ def lib():
     L.svsdf_check_sub_sw_collision.argtypes = [C.c_void_p, C.c_size_t, _dp, _dp, C.POINTER(C.c_size_t), _dp, _u8p]
     L.svsdf_shape_kernels.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, _u8p, _u8p, _dp,
                                       C.POINTER(C.c_int)]
+    L.svsdf_frontend_set_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double]
+    L.svsdf_frontend_yaw_free.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_size_t, _ip]
+    L.svsdf_kernel_bfs.argtypes = [C.c_ulonglong, C.c_int, C.c_double, _dp, _ip]
+    L.svsdf_astar_successors.argtypes = [C.c_void_p, C.c_size_t, _ip, _dp, _u8p, _dp, _u8p]
     L.svsdf_mesh_outline.argtypes = [_dp, C.c_size_t, _ip, C.c_size_t, C.c_double, _dp, C.c_size_t,
                                      C.POINTER(C.c_size_t), _ip]
     L.svsdf_mesh_outline_obj.argtypes = [C.c_char_p, C.c_double, _dp, C.c_size_t, C.POINTER(C.c_size_t), _ip]
@@ -220,6 +225,17 @@ def _f64(a):
 def _colmajor(m):
     """(rows, cols) array -> flat column-major copy (Eigen's default storage)."""
     return np.asfortranarray(_f64(m)).ravel(order="F").copy()
+
+
+def kernel_bfs(mask, kernel_count, father_yaw):
+    """checkKernelValue + visit_kernels_by_distance (sw_manager.hpp:1103-1169) on one cell's word of the yaw-free
+    table (svsdf_kernel_bfs; host only).  Returns (child_yaw, kernel_index), None when no kernel is free within the
+    search depth; raises ValueError for a yaw whose kernel index falls outside [0, kernel_count)."""
+    cy, ki = C.c_double(0.0), C.c_int(0)
+    rc = lib().svsdf_kernel_bfs(int(mask) & 0xFFFFFFFFFFFFFFFF, int(kernel_count), float(father_yaw), C.byref(cy), C.byref(ki))
+    if rc < 0:
+        raise ValueError(f"svsdf_kernel_bfs({int(mask):#x}, {kernel_count}, {father_yaw!r}) rejected its arguments ({rc})")
+    return (cy.value, ki.value) if rc else None
 
 
 def shape_id_from_inputdata(inputdata):
@@ -680,6 +696,39 @@ class SvsdfContext:
                                              m.ctypes.data_as(u8), b.ctypes.data_as(u8), _p(yaws), C.byref(n)),
                   "svsdf_shape_kernels")
         return m.astype(bool), b, yaws, n.value
+
+    def frontend_set_map(self, occupancy_map, kernel_size, kernel_count, safemargin):
+        """Make `occupancy_map` (an OccupancyMap) the resident front-end map: layer 0 as a bitmap, the yaw kernels of
+        shape_kernels at the map's resolution, and the yaw-free table (svsdf_frontend_set_map)."""
+        self._chk(self.L.svsdf_frontend_set_map(self.ctx, occupancy_map.h, int(kernel_size), int(kernel_count),
+                                                float(safemargin)), "svsdf_frontend_set_map")
+
+    def yaw_free(self):
+        """The yaw-free table as a uint64 (X, Y) array: bit k of [ix, iy] is set iff kernelConv<true>(k, (ix, iy, 0))
+        (sw_manager.hpp:1033-1099) returns true."""
+        dims = (C.c_int * 2)()
+        self._chk(self.L.svsdf_frontend_yaw_free(self.ctx, None, 0, dims), "svsdf_frontend_yaw_free")
+        out = np.zeros((dims[0], dims[1]), dtype=np.uint64)
+        self._chk(self.L.svsdf_frontend_yaw_free(self.ctx, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), out.size, dims),
+                  "svsdf_frontend_yaw_free")
+        return out
+
+    def astar_successors(self, parent_ij, parent_yaw):
+        """AstarGetSucc's test (front_end_Astar.hpp:192-241) of the 9 neighbours of every parent on the resident map.
+        parent_ij: (n, 2) cell indices, parent_yaw: (n,).  Returns (ok (n, 9) bool, child_yaw (n, 9), stage (n, 9) uint8),
+        slot 3 (i + 1) + (j + 1); stage 0 accepted, 1 invalid, 2 occupied, 3 no yaw kernel, 4 sub-swept collision."""
+        ij = np.ascontiguousarray(parent_ij, dtype=np.int32).reshape(-1, 2)
+        yaw = _f64(parent_yaw).reshape(-1)
+        n = len(ij)
+        if len(yaw) != n:
+            raise ValueError("astar_successors: one yaw per parent")
+        ok = np.zeros((n, 9), dtype=np.uint8)
+        cy = np.full((n, 9), np.nan)
+        stage = np.zeros((n, 9), dtype=np.uint8)
+        u8 = C.POINTER(C.c_ubyte)
+        self._chk(self.L.svsdf_astar_successors(self.ctx, n, ij.ctypes.data_as(_ip), _p(yaw), ok.ctypes.data_as(u8), _p(cy),
+                                                stage.ctypes.data_as(u8)), "svsdf_astar_successors")
+        return ok.astype(bool), cy, stage
 
     def debug_sdf_at(self, coeffs, T, points_xy, t):
         """SDF-at-time of (point, time) pairs on the device with its intermediates (svsdf_debug_sdf_at): (n, 8) array

@@ -289,6 +289,53 @@ int svsdf_map_gather(const svsdf_map *map, const double *centres_xyz, size_t nce
 /* ASCII PCD v0.7, FIELDS x y z (src/plan_manager/pcds/map_*.pcd); xyz may be NULL to query n. */
 int svsdf_pcd_read_ascii(const char *path, float *xyz, size_t capacity, size_t *n);
 
+/* ---- front end: yaw-kernel free-space table and batched A* successor test (device) ---------- */
+/* AstarPathSearcher::AstarGetSucc (src/planner_algorithm/include/planner_algorithm/front_end_Astar.hpp:192-241) tests
+ * each of the 9 neighbours vi of a node in four steps: (1) isIndexValid(vi) && !isIndexOccupiedFlate(vi, 0)
+ * (src/map_manager/src/Gridmap3D.cpp:73-133, 213-237); (2) checkKernelValue(father yaw, child yaw, vi)
+ * (sw_manager.hpp:1158-1169), a breadth-first search over the yaw kernels around the father's yaw
+ * (visit_kernels_by_distance, :1103-1156) that stops at the first kernel whose bit convolution kernelConv<true>
+ * (:1033-1099) with the inflated map (generateMapKernel2D, src/map_manager/include/map_manager/PCSmap_manager.h:
+ * 81-108) is empty -- that kernel decides the child's yaw; (3) getPointsInAABB2D(child centre, kernel_size/2+1,
+ * kernel_size/2+1) (PCSmap_manager.h:137-158); (4) checkSubSWCollision(father, child, points) (sw_manager.hpp:
+ * 1171-1211).  The entries below run all four on data resident on the device.
+ *
+ * svsdf_frontend_set_map: takes layer iz = 0 of the map's occupancy grid (what generateMapKernel2D and
+ * getPointsInAABB2D read), builds the byte kernels of svsdf_shape_kernels on the device at the map's own resolution
+ * (kernelConv overlays kernel cells on map cells one to one), and computes the yaw-free table: one 64-bit word per cell
+ * (ix, iy), bit k set iff kernelConv<true>(k, (ix, iy, 0)) returns true -- the inflated map is (X + 2 side) x
+ * (Y + 2 side) with side = (kernel_size - 1) / 2, the cell index itself is the box's minimum corner in it, outside the
+ * map is free, and the bits the reference reads past a row only meet kernel columns >= kernel_size, which are zero.
+ * The bitmap, the grid geometry and the table stay resident in the context until the next call or svsdf_destroy.
+ * SVSDF_ERR_INVALID with a message: Polygon (as in svsdf_shape_kernels), an even or non-positive kernel_size,
+ * kernel_size > 63 or kernel_count > 64 (a kernel row and a cell's mask are one word each; the reference's yaml has
+ * 17 and 18), a null or empty map.  A multi-device context uses its first device, like the other front-end entries. */
+int svsdf_frontend_set_map(svsdf_ctx *ctx, const svsdf_map *map, int kernel_size, int kernel_count, double safemargin);
+/* The yaw-free table, mask_out[ix * dims2[1] + iy]; mask_out may be NULL to query dims2 = {X, Y}. */
+int svsdf_frontend_yaw_free(const svsdf_ctx *ctx, unsigned long long *mask_out, size_t capacity, int dims2[2]);
+/* checkKernelValue + visit_kernels_by_distance (sw_manager.hpp:1103-1169) on one cell's word of the table; host only,
+ * no context.  Returns 1 and writes *child_yaw, *kernel_index when a kernel is found, 0 when none (outputs untouched),
+ * negative for a bad argument (outputs untouched).  The device code of svsdf_astar_successors calls the same function.
+ * father_i = int(kernel_count * ((father_yaw + pi) / (2 * pi))) with pi = 3.1415926536 (sw_manager.hpp:20, not the PI
+ * of the yaw table) truncates: fed the child yaws this function hands out it lands on i - 1 for some i (2 and 11 at 18
+ * kernels).  An index outside [0, kernel_count) -- father_yaw >= pi, NaN, father_yaw <= -pi - 2 pi / kernel_count --
+ * is an error (the reference indexes past its arrays).  Search order: pop, test, on failure push x - 1 then x + 1
+ * (wrapped, unvisited only), give up after more than 10 pops: at most 11 kernels, s, s-1, s+1, ..., s-5, s+5.
+ * child_yaw = 2 * pi * index / kernel_count - pi, evaluated left to right.  1 <= kernel_count <= 64. */
+int svsdf_kernel_bfs(unsigned long long free_mask, int kernel_count, double father_yaw, double *child_yaw,
+                     int *kernel_index);
+/* The successor test of n nodes in one call: parent p = cell parent_ij[2p], parent_ij[2p+1] with yaw parent_yaw[p];
+ * results at 9 p + 3 (i + 1) + (j + 1) for the neighbour (i, j), i and j from -1 to 1 (the reference's loop order,
+ * centre included).  ok_out: 1 where the reference accepts the neighbour.  stage_out (may be NULL): 0 accepted,
+ * 1 index invalid, 2 cell occupied, 3 no yaw kernel found, 4 sub-swept-volume collision.  child_yaw_out: the yaw
+ * checkKernelValue chose, for stages 0 and 4; NaN elsewhere.  father = (centre of the parent cell, parent yaw), child =
+ * (centre of the neighbour, chosen yaw), centres by getGridCubeCenter (Gridmap3D.cpp:184-195); obstacle points = centres
+ * of the occupied layer-0 cells in the index box of getPointsInAABB2D, half extent kernel_size/2 + 1 METRES (integer
+ * division, not scaled by the resolution).  SVSDF_ERR_INVALID: no map set, a parent outside the map or one whose yaw
+ * svsdf_kernel_bfs rejects (the message names the first). */
+int svsdf_astar_successors(svsdf_ctx *ctx, size_t n, const int *parent_ij, const double *parent_yaw,
+                           unsigned char *ok_out, double *child_yaw_out, unsigned char *stage_out);
+
 /* ---- mesh shapes (host; BASELINE config 5: "arbitrary .obj mesh, no analytic shape SDF") ------------------------ */
 /* The reference loads conf.inputdata with igl::read_triangle_mesh (src/utils/include/utils/Shape.hpp:281-313) and,
  * when the file's stem is not in its shape registry, plans with the generic Polygon shape over an outline

@@ -1,0 +1,101 @@
+"""Time the resident front-end map and the batched successor test beside the route a caller had before them.
+
+On the reference's star demo map (resolution 1, kernels 17 / 18, margin 0.5) and on a synthetic 1024 x 1024 map at 30 %
+occupancy:
+  - frontend_set_map (bitmap upload, byte kernels, yaw-free table),
+  - astar_successors for 1, 64 and 4096 parents,
+  - the host route for the same edges, given the child yaws: OccupancyMap.gather per child, then one
+    check_sub_sw_collision over all of them (it covers step 4 only: the yaws come from astar_successors here).
+Median of --steps runs after --warmup.  Prints one line per measurement; nothing is asserted.
+
+    python tools/frontend_timing.py [--steps 20] [--warmup 3] [--maps star synthetic]
+"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "implicit-svsdf-planner_amd")]
+
+import numpy as np  # noqa: E402
+
+import svsdf_amd  # noqa: E402
+from svsdf_amd import workload  # noqa: E402
+
+KS, KC, MARGIN = 17, 18, 0.5
+
+
+def _median_ms(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(steps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def _synthetic_cloud(n, rng):
+    g = rng.random((n, n)) < 0.3
+    ii, jj = np.nonzero(g)
+    c = np.column_stack([ii + 0.5, jj + 0.5, np.full(len(ii), 0.5)])
+    return np.vstack([[[0.0, 0.0, 0.0], [float(n), float(n), 1.0]], c]).astype(np.float32)
+
+
+def _host_route(ctx, om, info, ij, yaw, cyaw, stage):
+    """What the same edges cost without the resident map: one gather per child, one batched collision check."""
+    bmin = info["bmin"]
+    half = [float(KS // 2 + 1)] * 2 + [0.0]
+    sel = np.argwhere((stage == 0) | (stage == 4))
+
+    def run():
+        fs, cs, pts = [], [], []
+        for p, s in sel:
+            vi, vj = ij[p, 0] + s // 3 - 1, ij[p, 1] + s % 3 - 1
+            c = np.array([vi + 0.5 + bmin[0], vj + 0.5 + bmin[1], 0.0])
+            pts.append(om.gather(c[None], half)[:, :2])
+            fs.append([ij[p, 0] + 0.5 + bmin[0], ij[p, 1] + 0.5 + bmin[1], yaw[p]])
+            cs.append([c[0], c[1], cyaw[p, s]])
+        if fs:
+            ctx.check_sub_sw_collision(np.array(fs), np.array(cs), pts)
+    return run, len(sel)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--maps", nargs="*", default=["star", "synthetic"])
+    ap.add_argument("--host-max", type=int, default=64, help="largest parent batch the host route is timed for")
+    a = ap.parse_args()
+    rng = np.random.default_rng(20240607)
+    hand_out = [2 * 3.1415926536 * k / KC - 3.1415926536 for k in range(KC)]
+    ctx = svsdf_amd.SvsdfContext(shape="star", device=0)
+    for name in a.maps:
+        cloud = np.array(workload._assets()["maps"]["star"], dtype=np.float32) if name == "star" else _synthetic_cloud(1024, rng)
+        om = svsdf_amd.OccupancyMap(cloud, resolution=1.0)
+        info = om.info()
+        X, Y = info["dims"][:2]
+        ms = _median_ms(lambda: ctx.frontend_set_map(om, KS, KC, MARGIN), a.steps, a.warmup)
+        free = ctx.yaw_free()
+        print(f"{name} {X} x {Y}: frontend_set_map {ms:.3f} ms; cells with a free yaw {int((free != 0).sum())} of {free.size}",
+              flush=True)
+        for n in (1, 64, 4096):
+            ij = np.column_stack([rng.integers(0, X, n), rng.integers(0, Y, n)]).astype(np.int32)
+            yaw = np.array([hand_out[k] for k in rng.integers(0, KC, n)])
+            ms = _median_ms(lambda: ctx.astar_successors(ij, yaw), a.steps, a.warmup)
+            ok, cyaw, stage = ctx.astar_successors(ij, yaw)
+            hist = np.bincount(stage.ravel(), minlength=5).tolist()
+            line = f"{name} {n} parents: astar_successors {ms:.3f} ms; stages 0..4 {hist}"
+            if n <= a.host_max:
+                run, edges = _host_route(ctx, om, info, ij, yaw, cyaw, stage)
+                hms = _median_ms(run, a.steps, a.warmup)
+                line += f"; host gather + check_sub_sw_collision of the {edges} edges with a yaw {hms:.3f} ms"
+            print(line, flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
