@@ -312,10 +312,13 @@ k_succ(ShapeParams sp, FrontMapDev fm, const int *__restrict__ parent_ij, const 
 // through the very pose_at / sdf_from_pose the solve kernels inline, with the intermediates: out[8 i ..] = sdf, x, y, cos,
 // sin, body-frame x, body-frame y, piece-local-time path taken (0 cumulative, 1 / 2 chain).  One wave per block: the
 // faithful piece-time chain works on whole waves.
-template <int SHAPE>
+// Scl = ScaleDev: the same under a time-varying scale (§4c), getSDFAtTimeStamp<true>, out8[5..6] = the scaled body-frame point u.
+template <int SHAPE, typename... Scl>
 __global__ void __launch_bounds__(64)
 k_debug_sdf_at(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__restrict__ pxy, const double *__restrict__ t_,
-               int n, double *__restrict__ out) {
+               int n, double *__restrict__ out, Scl... scl_arg) {
+  constexpr bool SC = ScaleArg<Scl...>::SC;
+  const ScaleDev scl = ScaleArg<Scl...>::get(scl_arg...);
   extern __shared__ double dbg_lds[];
   const TrajL tr = stage_traj(trg, dbg_lds);
   const int i = blockIdx.x * 64 + threadIdx.x;
@@ -323,31 +326,19 @@ k_debug_sdf_at(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__
   PieceCache pc = piece_cache_init();
   const Pose p = pose_at(tr, t_[i], pc);
   const double px = pxy[2 * i], py = pxy[2 * i + 1];
-  const double dx = px - p.x, dy = py - p.y;
-  const double rx = p.cs * dx + p.sn * dy;
-  const double ry = (-p.sn) * dx + p.cs * dy;
   double *o = out + 8 * (size_t)i;
-  o[0] = sdf_from_pose<SHAPE>(sp, p, px, py);
-  o[1] = p.x; o[2] = p.y; o[3] = p.cs; o[4] = p.sn; o[5] = rx; o[6] = ry; o[7] = (double)tr.exact;
-}
-
-// the same under a time-varying scale (§4c): getSDFAtTimeStamp<true>, out8[5..6] = the scaled body-frame point u
-template <int SHAPE>
-__global__ void __launch_bounds__(64)
-k_debug_sdf_at_sc(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__restrict__ pxy, const double *__restrict__ t_,
-                  int n, double *__restrict__ out, ScaleDev scl) {
-  extern __shared__ double dbg_lds[];
-  const TrajL tr = stage_traj(trg, dbg_lds);
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i >= n) return;
-  PieceCache pc = piece_cache_init();
-  const Pose p = pose_at(tr, t_[i], pc);
-  const double px = pxy[2 * i], py = pxy[2 * i + 1];
-  double i00, i11, rx, ry;
-  scale_inv(scl, t_[i], i00, i11);
-  rel_scaled(p, px, py, i00, i11, rx, ry);
-  double *o = out + 8 * (size_t)i;
-  o[0] = shape_sdf<SHAPE>(sp, rx, ry);
+  double rx, ry;
+  if constexpr (SC) {
+    double i00, i11;
+    scale_inv(scl, t_[i], i00, i11);
+    rel_scaled(p, px, py, i00, i11, rx, ry);
+    o[0] = shape_sdf<SHAPE>(sp, rx, ry);
+  } else {
+    const double dx = px - p.x, dy = py - p.y;
+    rx = p.cs * dx + p.sn * dy;
+    ry = (-p.sn) * dx + p.cs * dy;
+    o[0] = sdf_from_pose<SHAPE>(sp, p, px, py);
+  }
   o[1] = p.x; o[2] = p.y; o[3] = p.cs; o[4] = p.sn; o[5] = rx; o[6] = ry; o[7] = (double)tr.exact;
 }
 

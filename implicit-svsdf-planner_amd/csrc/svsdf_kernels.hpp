@@ -36,6 +36,9 @@ namespace svsdf {
 #ifndef SVSDF_FUSED_PASS
 #define SVSDF_FUSED_PASS 1   // a wave's LAST open descent: derivative + both signs of the ladder in one step (descend_from_seed)
 #endif
+#ifndef SVSDF_CLOCK_PROBE
+#define SVSDF_CLOCK_PROBE 1   // k_solve: the first wave of a batch's first launch times itself (BatchCtl::clk)
+#endif
 constexpr int kMaxPieces = 128;   // = SVSDF_MAX_PIECES (64 until round 5); sizes TrajDev and the result rows, nothing on the hot path
 constexpr int kMaxSlots = 24;   // GSIP samples per round: 2, 6, 18, 21, 21, ... (SWM:60-71,105-110)
 constexpr int kMaxRounds = 9;   // SWM:995 (iter > 8)
@@ -459,6 +462,21 @@ __device__ __forceinline__ double sdf_at(const TrajL &tr, const ShapeParams &sp,
 // ---- time-varying robot scale (the reference's useScale path, SWM:17 / 495-535)
 // S(t) = diag(s_x(t), s_y(t), 1), s_a(t) = c_a + sin(w_a t + phi_a) A_a, evaluated per evaluation with the device sin.
 struct ScaleDev { double cx, ax, wx, phx, cy, ay, wy, phy; };
+// A kernel with a rigid and a scaled form (k_solve, k_classify, k_reduce, k_debug_sdf_at) takes the schedule as a parameter
+// pack `Scl... scl_arg`: empty for the rigid kernel -- its arguments, hidden ones included, are then exactly those of a
+// kernel without it -- and exactly ScaleDev for the scaled one.  ScaleArg<Scl...>::SC says which form this is, ::get(scl_arg...)
+// is the schedule (ScaleDev{} in the rigid kernel, where no SC = false path reads it).
+template <typename... Scl>
+struct ScaleArg {
+  static_assert(sizeof...(Scl) == 0, "the scale pack is empty (rigid kernel) or exactly ScaleDev (scaled kernel)");
+  static constexpr bool SC = false;
+  static __device__ __forceinline__ ScaleDev get() { return ScaleDev{}; }
+};
+template <>
+struct ScaleArg<ScaleDev> {
+  static constexpr bool SC = true;
+  static __device__ __forceinline__ const ScaleDev &get(const ScaleDev &s) { return s; }
+};
 // S(t)^-1 as Eigen's 3x3 inverse() forms it for a diagonal S: cofactors times 1 / det, det = s_y s_x (+ zeros), so
 // i00 = s_y (1 / (s_x s_y)) and i11 = s_x (1 / (s_x s_y)) -- not 1 / s_x, 1 / s_y.  S = I gives exactly 1, 1.
 __device__ __forceinline__ void scale_inv(const ScaleDev &s, double t, double &i00, double &i11) {
@@ -1503,30 +1521,132 @@ __device__ __forceinline__ void descend_from_seed(const TrajL &tr, const double 
 //    per-trial re-evaluation returns the same number.
 // LDS: [Polygon edges 6 nverts (kPolygonLds only) | pose table 4K | chunks 4*nch | trajectory 20N+1] doubles, then
 // ladder_lds_bytes(G) per wave of the block (descent state of its 64 / G groups).
+// Under a time-varying scale S(t) (Scl = ScaleDev, §4c): same layer-1 scan, layers 2-4 rigid, the descent scaled.  The host
+// passes no cull there (cull_thresh = inf, rot = null): the culls bound the RIGID map.
 // ---------------------------------------------------------------------------------------------
 // (Polygon: 172 VGPRs would mean 2 waves per SIMD for a kernel that waits on its candidate-record loads; asking for 3
 // blocks of 4 waves per CU caps it at 168 with two spilled registers: C5 43.3 -> 38.7 ms)
-template <int SHAPE, int G, int U>
+template <int SHAPE, int G, int U, typename... Scl>
 __global__ void __launch_bounds__(kBlock, is_polygon<SHAPE>() ? 3 : SVSDF_SOLVE_WAVES)
 k_solve(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Pose *__restrict__ pose_g,
         const Chunk *__restrict__ chunks_g, ShapeParams sp, QuerySet qs, double *__restrict__ out_sdf,
         double *__restrict__ out_t, int prune /* bit 0: exact chunk pruning; bit 1: one query per wave; bits 2, 3: layer tables */, BatchCtl *__restrict__ ctl, int work_idx, double cull_thresh,
-        const double *__restrict__ rot, double slack_max, const Pose *__restrict__ ltab_g) {
-  constexpr bool SC = false;
-  const ScaleDev scl{};
-#include "svsdf_body_solve.hpp"
-}
-
-// k_solve under a time-varying scale S(t) (§4c): same layer-1 scan, layers 2-4 rigid, the descent scaled.  The host passes
-// no cull (cull_thresh = inf, rot = null): the culls bound the RIGID map.
-template <int SHAPE, int G, int U>
-__global__ void __launch_bounds__(kBlock, is_polygon<SHAPE>() ? 3 : SVSDF_SOLVE_WAVES)
-k_solve_sc(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Pose *__restrict__ pose_g,
-           const Chunk *__restrict__ chunks_g, ShapeParams sp, QuerySet qs, double *__restrict__ out_sdf,
-           double *__restrict__ out_t, int prune, BatchCtl *__restrict__ ctl, int work_idx, double cull_thresh,
-           const double *__restrict__ rot, double slack_max, ScaleDev scl, const Pose *__restrict__ ltab_g) {
-  constexpr bool SC = true;
-#include "svsdf_body_solve.hpp"
+        const double *__restrict__ rot, double slack_max, Scl... scl_arg, const Pose *__restrict__ ltab_g /* layer pose tables or null */) {
+  constexpr bool SC = ScaleArg<Scl...>::SC;
+  const ScaleDev scl = ScaleArg<Scl...>::get(scl_arg...);
+  extern __shared__ double solve_lds[];
+  int n;
+  const long long total = qs_total(qs, n);
+  if (total <= 0 || (long long)blockIdx.x * (((prune & 2) != 0) ? (blockDim.x >> 6) : (blockDim.x / G)) >= total) return;
+  const int K = trg->K;
+  const int nch = (K + kChunk - 1) / kChunk;
+  stage_poly_edges<SHAPE>(sp, solve_lds);
+  double *tab_lds = solve_lds + poly_lds_doubles<SHAPE>(sp.nverts);
+  Pose *pose = reinterpret_cast<Pose *>(tab_lds);
+  Chunk *chunks = reinterpret_cast<Chunk *>(tab_lds + 4 * (size_t)K);
+  {
+    const double *src = reinterpret_cast<const double *>(pose_g);
+    for (int i = threadIdx.x; i < 4 * K; i += blockDim.x) tab_lds[i] = src[i];
+    const double *srcc = reinterpret_cast<const double *>(chunks_g);
+    for (int i = threadIdx.x; i < 4 * nch; i += blockDim.x) tab_lds[4 * (size_t)K + i] = srcc[i];
+  }
+  const TrajL tr = stage_traj(trg, tab_lds + 4 * (size_t)K + 4 * (size_t)nch);  // ends with __syncthreads
+  // per-wave descent state behind the trajectory (16-byte aligned: the tables before it are whole doubles, rounded up)
+  const size_t tables = poly_lds_doubles<SHAPE>(sp.nverts) + 4 * (size_t)K + 4 * (size_t)nch + (size_t)traj_lds_doubles(tr.N);
+  char *wave_lds = reinterpret_cast<char *>(solve_lds + ((tables + 1) & ~(size_t)1)) + (threadIdx.x >> 6) * ladder_lds_bytes(G);
+  const int li = Grp<G>::li();
+  unsigned n_eval = 0, n_scan = 0, n_solved = 0, n_culled = 0, n_spec = 0;
+  unsigned long long sc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // SVSDF_SITE_STATS builds only
+  const bool clk_probe = SVSDF_CLOCK_PROBE && work_idx == 0 && blockIdx.x == 0 && threadIdx.x < 64;   // (wave-uniform; BatchCtl::clk)
+  // (the start values wait in the control block itself, not in four vector registers that would live through the whole kernel)
+  volatile unsigned long long *clk = ctl->clk;
+  if (clk_probe && threadIdx.x == 0) { clk[0] = (unsigned long long)clock64(); clk[1] = (unsigned long long)wall_clock64(); }
+  // Work distribution: a wave's FIRST 64 / G queries are its own (wave index: no atomic), the following ones come from
+  // the launch's cursor.  (All waves of a launch start together: with a fetch first, their 3000 atomics on one address
+  // take ~ 12 ns each, one after the other -- the last wave would start ~ 37 us late, in every launch of the chain.)
+  // `prune` bit 1 (round 6; launches of a few hundred queries, i.e. the main solve at the reference's own scale): ONE query per
+  // wave -- the other lane groups stay empty -- so that every descent is "the wave's last open one" from its first pass on and
+  // takes the fused pass (derivative + both signs of the ladder in one step: descend_from_seed) instead of two dependent
+  // steps per pass.  The chip has a wave slot for every query there; the launch is a chain of dependent evaluations.
+  const bool solo = (prune & 2) != 0;
+  // `prune` bits 2 / 3: the launch carries the pose table of scan layer 2 / of layer 3 behind it (LayerTab, read by this wave only)
+  if ((threadIdx.x & 63) == 0) {
+    LayerTab *lt = wave_layer_tab<G>(wave_lds);
+    lt->l2 = (prune & 4) ? ltab_g : nullptr;
+    lt->l3 = (prune & 8) ? ltab_g + (size_t)K * kLayerSteps : nullptr;
+  }
+  prune &= 1;
+  const long long per_wave = solo ? 1 : 64 / G;
+  const long long n_static = (long long)gridDim.x * (blockDim.x >> 6) * per_wave;
+  for (int guard = 0; guard < (1 << 26); ++guard) {
+    long long wave_base, gq;
+    if (guard == 0) {
+      wave_base = (long long)((blockIdx.x * blockDim.x + threadIdx.x) >> 6) * per_wave;
+      gq = wave_base + (long long)((threadIdx.x & 63) / G);
+    } else {
+      gq = fetch_work<G>(&ctl->work[work_idx], wave_base, (int)per_wave) + n_static;
+      wave_base += n_static;
+    }
+    if (wave_base >= total) break;
+    double px = 0.0, py = 0.0;
+    size_t slot = 0;
+    bool live = gq < total && (long long)((threadIdx.x & 63) / G) < per_wave;
+    if (live) live = qs_slot(qs, n, gq, slot);
+    if (live) {
+      px = qs.qx[slot]; py = qs.qy[slot];
+      live = (px == px);  // NaN marks an unused slot (whole group)
+    }
+    // ---- choiceTInit layer 1 over the pose table (or the seed k_round already found for a GSIP sample)
+    double best_d = 1e9;
+    int best_k = 0x7fffffff;
+    bool culled = false;
+    const unsigned long long t_scan0 = SVSDF_SITE_CLOCK();
+    if (live) {
+    if (qs.seed_k) {
+      best_k = qs.seed_k[slot];
+      best_d = qs.seed_d[slot];
+    }
+    if (!qs.seed_k || best_k < 0) {   // no seed for this query (main points, cheap-bound samples, unscanned lazy samples)
+      scan_layer1<SHAPE, G>(sp, pose, chunks, K, nch, px, py, prune, cull_thresh, best_d, best_k, culled, n_scan, nullptr, -1,
+                            sc, rot, slack_max);
+    }
+    if (culled && li == 0) { out_sdf[slot] = best_d; out_t[slot] = 0.0; ++n_culled; }
+    }  // live
+    const bool on = live && !culled;
+    SVSDF_SITE_CYCLES(sc, 8, t_scan0);
+    double x = 0.0, fx = 0.0;
+    descend_from_seed<SHAPE, G, U, SC>(tr, tk, sp, px, py, on, best_k, best_d, x, fx, n_eval, n_spec, sc, wave_lds, scl, true);   // whole wave
+    if (on && li == 0) {
+      out_sdf[slot] = fx;
+      out_t[slot] = x;
+      ++n_solved;
+    }
+  }
+  if (clk_probe && threadIdx.x == 0) {
+    clk[0] = (unsigned long long)clock64() - clk[0];
+    clk[1] = (unsigned long long)wall_clock64() - clk[1];
+  }
+  unsigned long long te = (unsigned long long)n_eval + n_scan, ts = n_solved, tc = n_scan, tu = n_culled, tp = n_spec;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    te += __shfl_xor(te, m, 64); ts += __shfl_xor(ts, m, 64); tc += __shfl_xor(tc, m, 64); tu += __shfl_xor(tu, m, 64);
+    tp += __shfl_xor(tp, m, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && (te || tu)) {
+    StatSlot *ss = stat_slot(ctl->stat);
+    atomicAdd(&ss->evals, te); atomicAdd(&ss->solves, ts); atomicAdd(&ss->scan, tc);
+    if (tu) atomicAdd(&ss->culled, tu);
+    if (tp) atomicAdd(&ss->spec, tp);
+  }
+#ifdef SVSDF_SITE_STATS
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    unsigned long long v = sc[i];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&stat_slot(ctl->stat)->pad[i], v);
+  }
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1577,27 +1697,102 @@ struct GsipState {
 
 // Per main point after the first solve: exterior -> FD gradient (getGradPrelAtTimeStamp,
 // SWM:779-788) and done; interior -> GSIP init (SWM:926-963), first round opened by k_round.
-template <int SHAPE>
+// (Scl = ScaleDev: getGradPrelAtTimeStamp<true> (SWM:779-797), the body-frame finite difference at the SCALED u at t*; §4c)
+template <int SHAPE, typename... Scl>
 __global__ void __launch_bounds__(kBlock)
 k_classify(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__restrict__ px_,
            const double *__restrict__ py_, const double *__restrict__ sdf_,
            const double *__restrict__ t_, double *__restrict__ res_sdf,
            double *__restrict__ res_t, double *__restrict__ res_gx, double *__restrict__ res_gy,
-           GsipState gs, BatchCtl *__restrict__ ctl, int *__restrict__ n_int, int icap) {
-  constexpr bool SC = false;
-  const ScaleDev scl{};
-#include "svsdf_body_classify.hpp"
-}
-// (SC: getGradPrelAtTimeStamp<true> (SWM:779-797), the body-frame finite difference at the SCALED u at t*; §4c)
-template <int SHAPE>
-__global__ void __launch_bounds__(kBlock)
-k_classify_sc(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__restrict__ px_,
-              const double *__restrict__ py_, const double *__restrict__ sdf_,
-              const double *__restrict__ t_, double *__restrict__ res_sdf,
-              double *__restrict__ res_t, double *__restrict__ res_gx, double *__restrict__ res_gy,
-              GsipState gs, BatchCtl *__restrict__ ctl, int *__restrict__ n_int, int icap, ScaleDev scl) {
-  constexpr bool SC = true;
-#include "svsdf_body_classify.hpp"
+           GsipState gs, BatchCtl *__restrict__ ctl, int *__restrict__ n_int, int icap, Scl... scl_arg) {
+  constexpr bool SC = ScaleArg<Scl...>::SC;
+  const ScaleDev scl = ScaleArg<Scl...>::get(scl_arg...);
+  extern __shared__ double classify_lds[];
+  const TrajL tr = stage_traj(trg, classify_lds);
+  const int start = ctl->start, count = ctl->count;
+  const int lane = (int)(threadIdx.x & 63);
+  // (wave-uniform trip count: the interior lanes of a wave take their indices together, below)
+  for (int e0 = (int)((blockIdx.x * blockDim.x + threadIdx.x) & ~63u); e0 < count; e0 += gridDim.x * blockDim.x) {
+    const int e = e0 + lane;
+    const bool in_range = e < count;
+    const int i = start + (in_range ? e : 0);
+    const double px = px_[i], py = py_[i];
+    const double sdf = sdf_[i], ts = t_[i];
+    const bool inter = in_range && !(sdf > 0);
+    double vx = 0.0, vy = 0.0, w = 0.0;
+    if (in_range && sdf > 0) {  // outside case (SWM:921-924)
+      int piece = 0;
+      const Pose p = pose_at(tr, ts, piece);
+      double rx, ry;
+      if constexpr (SC) {
+        double i00, i11;
+        scale_inv(scl, ts, i00, i11);
+        rel_scaled(p, px, py, i00, i11, rx, ry);
+      } else {
+        const double dx = px - p.x, dy = py - p.y;
+        rx = p.cs * dx + p.sn * dy;
+        ry = (-p.sn) * dx + p.cs * dy;
+      }
+      double gx, gy;
+      shape_grad<SHAPE>(sp, rx, ry, gx, gy);
+      res_sdf[i] = sdf; res_t[i] = ts; res_gx[i] = gx; res_gy[i] = gy;
+    } else if (inter) {
+      // interior: velocity at t* with the low-speed rescans (SWM:929-954)
+      double sl;
+      int piece = locate_local(tr, ts, 0, sl);
+      piece_vel(tr.c + piece * 18, sl, vx, vy, w);
+      if (sqrt(vx * vx + vy * vy + w * w) < 0.01) {
+        if (ts < 0.1) {
+          for (double t_scan = ts; t_scan <= tr.dur; t_scan += 0.1) {
+            piece = locate_local(tr, t_scan, piece, sl);
+            piece_vel(tr.c + piece * 18, sl, vx, vy, w);
+            if (sqrt(vx * vx + vy * vy + w * w) >= 0.01) break;
+          }
+        } else if (ts > tr.dur - 0.1) {
+          for (double t_scan = ts; t_scan >= 0; t_scan -= 0.1) {
+            piece = locate_local(tr, t_scan, piece, sl);
+            piece_vel(tr.c + piece * 18, sl, vx, vy, w);
+            if (sqrt(vx * vx + vy * vy + w * w) >= 0.01) break;
+          }
+        }
+      }
+    }
+    // compact interior indices, one block of consecutive ones per wave (one atomic for the wave instead of one per
+    // point; neighbouring points keep neighbouring entries in the interior-sized arrays)
+    const unsigned long long mi = __ballot(inter);
+    if (mi == 0ull) continue;   // wave-uniform
+    const int leader = __ffsll((long long)mi) - 1;
+    int base_i = 0;
+    if (lane == leader) base_i = atomicAdd(n_int, __popcll(mi));
+    base_i = __shfl(base_i, leader, 64);
+    const int ia_ = base_i + __popcll(mi & ((1ull << lane) - 1ull));
+    const bool kept = inter && ia_ < icap;
+    if (inter && !kept) {   // no room: dropped (reads as inactive); the host sees n_int > icap, grows the arrays and repeats
+      res_sdf[i] = 1e300; res_t[i] = ts; res_gx[i] = 0.0; res_gy[i] = 0.0;
+    }
+    const unsigned long long mk = __ballot(kept);
+    if (mk == 0ull) continue;
+    const int leader2 = __ffsll((long long)mk) - 1;
+    int base_a = 0;
+    if (lane == leader2) base_a = atomicAdd(&ctl->n_active[0], __popcll(mk));
+    base_a = __shfl(base_a, leader2, 64);
+    if (kept) {
+      const int a = base_a + __popcll(mk & ((1ull << lane) - 1ull));
+      const size_t ia = (size_t)ia_;
+      // SampleSet2D::initSet (SWM:73-103)
+      double theta0 = atan2(vx, -vy);
+      if (theta0 < 0) theta0 += 2 * kPI;
+      gs.pt[ia] = i;
+      gs.r[ia] = 10;               // r0 (SWM:927)
+      gs.theta0[ia] = theta0;
+      gs.theta_res[ia] = kPI + 0.1;
+      gs.iter[ia] = 1;
+      gs.nsamp[ia] = 0;
+      gs.phase[ia] = kPhaseNew;
+      gs.list[0][start + a] = ia_;
+      res_t[i] = ts;  // real_t_star fallback
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2980,26 +3175,56 @@ __global__ void k_finish(const double *__restrict__ sums, int N, double *__restr
 // fuse == 0 (grids of more than 4 blocks): assembly only -- one block summing 19N+1 entries over hundreds of block partials
 // is a serial tail (57 us at C3's 512 blocks against k_final's 5 us with one wave PER entry): k_final and k_finish follow
 // as launches of their own there, where two launches are nothing against the evaluation.
+// Scl = ScaleDev: the position gradient under S(t*) (§4c).
 // ---------------------------------------------------------------------------------------------
+template <typename... Scl>
 __global__ void __launch_bounds__(kBlock)
 k_reduce(const TrajDev *__restrict__ trg, const double *__restrict__ px_, const double *__restrict__ py_, int P,
          const double *__restrict__ res_sdf, const double *__restrict__ res_t, const double *__restrict__ res_gx,
          const double *__restrict__ res_gy, double safety_hor, double weight_p, double *__restrict__ block_partials,
          int *__restrict__ nonfinite, double *__restrict__ out, const BatchCtl *__restrict__ ctl, int nbatch, int it_end,
-         int out_partial, int out_doubles, unsigned *__restrict__ ticket, double *__restrict__ host_out, int fuse) {
-  constexpr bool SC = false;
-  const ScaleDev scl{};
-#include "svsdf_body_reduce.hpp"
-}
-// k_reduce with the scaled position gradient (§4c)
-__global__ void __launch_bounds__(kBlock)
-k_reduce_sc(const TrajDev *__restrict__ trg, const double *__restrict__ px_, const double *__restrict__ py_, int P,
-            const double *__restrict__ res_sdf, const double *__restrict__ res_t, const double *__restrict__ res_gx,
-            const double *__restrict__ res_gy, double safety_hor, double weight_p, double *__restrict__ block_partials,
-            int *__restrict__ nonfinite, double *__restrict__ out, const BatchCtl *__restrict__ ctl, int nbatch, int it_end,
-            int out_partial, int out_doubles, unsigned *__restrict__ ticket, double *__restrict__ host_out, int fuse, ScaleDev scl) {
-  constexpr bool SC = true;
-#include "svsdf_body_reduce.hpp"
+         int out_partial, int out_doubles, unsigned *__restrict__ ticket, double *__restrict__ host_out, int fuse, Scl... scl_arg) {
+  constexpr bool SC = ScaleArg<Scl...>::SC;
+  const ScaleDev scl = ScaleArg<Scl...>::get(scl_arg...);
+  extern __shared__ double asm_lds[];
+  __shared__ unsigned s_last;
+  const bool one_block = gridDim.x == 1;   // up to 256 points (the reference's demo maps give 101 .. 139): nothing to wait for
+  assemble_body<SC>(trg, px_, py_, P, res_sdf, res_t, res_gx, res_gy, safety_hor, weight_p, block_partials, nonfinite, asm_lds, fuse && one_block, scl);
+  if (!fuse) return;
+  const int N = trg->N;
+  const int plen = 19 * N + 1;
+  const int nblocks = (int)gridDim.x;
+  double *sums = asm_lds + traj_lds_doubles(N);   // (the accumulator rows are free again: plen <= 4 plen doubles)
+  if (!one_block) {
+  __threadfence();   // this block's partials (and its non-finite count) are visible device-wide before its ticket is
+  __syncthreads();
+  if (threadIdx.x == 0) s_last = (atomicAdd(ticket, 1u) == gridDim.x - 1u) ? 1u : 0u;
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  // (other blocks wrote the partials: read at device scope, past this CU's vector cache)
+  auto part = [&](int e, int b) { return __hip_atomic_load(&block_partials[(size_t)e * nblocks + b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  {
+    // Up to 1024 points (the reference's own scale): one THREAD per entry.  k_final's wave leaves in lane 0, for lane
+    // values p_b = 0.0 + partial[e][b] (b < nblocks <= 4, zero beyond), the tree ((p0 + p2) + (p1 + p3)) -- the xor steps
+    // 32 .. 4 only add zeros to lanes 0 .. 3 -- so the same bits come from four independent loads per thread instead of a
+    // dependent load + butterfly per entry, one entry after the other (that loop cost 60 us of a 480 us callback).
+    for (int e = threadIdx.x; e < plen; e += blockDim.x) {
+      double p[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) p[b] = (b < nblocks) ? 0.0 + part(e, b) : 0.0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { p[0] += 0.0; p[1] += 0.0; p[2] += 0.0; p[3] += 0.0; }   // xor 32, 16, 8, 4: the partners hold zeros
+      sums[e] = (p[0] + p[2]) + (p[1] + p[3]);                                             // xor 2, then xor 1
+    }
+  }
+  }  // !one_block (one block: assemble_body left sums[e] = 0.0 + its partial in place)
+  __syncthreads();
+  finish_body(sums, N, out, ctl, nbatch, it_end, nonfinite, reinterpret_cast<unsigned long long *>(out + out_partial));
+  __threadfence();
+  __syncthreads();
+  if (host_out) copy_result_to_host(host_out, out, N, out_partial, out_doubles);
+  if (threadIdx.x == 0 && !one_block) *ticket = 0u;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // svsdf_launch.hpp -- host-side launchers of the shape-templated kernels.
 //
-// The kernels are specialised per shape id (17 shapes x lane-group widths x GSIP bound modes: ~250 kernels).  They are
+// The kernels are specialised per shape id (17 shapes x lane-group widths x GSIP bound modes: ~580 kernels).  They are
 // compiled in SVSDF_NSLICES translation units (svsdf_shape_slice.hip with -DSVSDF_SLICE=k holds the shapes with
 // id % SVSDF_NSLICES == k) so that the build runs in parallel; svsdf_pipeline.hip only sees these plain functions.
 #pragma once
@@ -17,7 +17,7 @@ struct SolveLaunch {   // arguments of k_solve<SHAPE, G, 1>
   const TrajDev *traj; const double *tk; const Pose *pose; const Chunk *chunks; ShapeParams sp; QuerySet qs;
   double *out_sdf, *out_t; int prune; BatchCtl *ctl; int work_idx; double cull_thresh;
   const double *rot; double slack_max;   // second exact cull (main points): per-chunk yaw allowance W_c h, max_c of the linear one
-  const ScaleDev *scl = nullptr;         // not null: k_solve_sc<SHAPE, G, 1> under this scale schedule (G in kScaledLanes)
+  const ScaleDev *scl = nullptr;         // not null: k_solve<SHAPE, G, 1, ScaleDev> under this scale schedule (G in kScaledLanes)
   const Pose *ltab = nullptr;            // layer-2 pose table, layer 3's behind it (k_layer_tables); `prune` bits 2 / 3 say which the launch uses
 };
 struct RoundLaunch {   // arguments of k_round<SHAPE, LP, MODE>
@@ -34,11 +34,15 @@ struct TailLaunch {    // arguments of k_tail<SHAPE, MODE, WAVES>
 struct ClassifyLaunch {   // arguments of k_classify<SHAPE>
   const TrajDev *traj; ShapeParams sp; const double *px, *py, *sdf, *t; double *res_sdf, *res_t, *res_gx, *res_gy;
   GsipState gs; BatchCtl *ctl; int *n_int; int icap;
-  const ScaleDev *scl = nullptr;   // not null: k_classify_sc<SHAPE>
+  const ScaleDev *scl = nullptr;   // not null: k_classify<SHAPE, ScaleDev>
 };
 // lane-group widths the scaled solve is instantiated for (§4c: a reduced plan space); scaled_lanes maps any width onto them
 constexpr int kScaledLanes[3] = {4, 8, 32};
 inline int scaled_lanes(int G) { return G >= 32 ? 32 : G >= 8 ? 8 : 4; }
+// The rigid / scaled choice of a launch site: f() for the rigid kernel, f(*scl) under a scale schedule.  A generic lambda
+// `[&](auto... scl)` then holds ONE launch expression for both: k_x<..., decltype(scl)...> with `scl...` among its arguments.
+template <typename F>
+auto with_scale(const ScaleDev *scl, F &&f) { return scl ? f(*scl) : f(); }
 
 // each returns false when the shape id is not compiled into the library (development builds)
 bool launch_k_solve(int shape, int G, unsigned grid, unsigned block, size_t lds, hipStream_t st, const SolveLaunch &a);

@@ -700,17 +700,13 @@ int reduce_and_read(svsdf_ctx *ctx, bool with_partial) {
     // launch whose last block writes the result to the device buffer and straight into the pinned host buffer (k_reduce);
     // larger ones: the assembly, then k_final (one wave per entry) and k_finish as launches of their own
     const int fuse = grid <= 4 ? 1 : 0;
-    if (ctx->scaled)   // the position gradient under S(t*) (§4c)
-      hipLaunchKernelGGL(k_reduce_sc, dim3(grid), dim3(kBlock), lds, ctx->stream, ctx->d_traj, ctx->d_px, ctx->d_py,
+    with_scale(ctx->scaled ? &ctx->scale : nullptr, [&](auto... scl) {   // scaled: the position gradient under S(t*) (§4c)
+      hipLaunchKernelGGL((k_reduce<decltype(scl)...>), dim3(grid), dim3(kBlock), lds, ctx->stream, ctx->d_traj, ctx->d_px, ctx->d_py,
                          (int)ctx->P, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
                          ctx->cfg.safety_hor, ctx->cfg.weight_p, ctx->d_block_partials, ctx->d_nonfinite, ctx->d_out,
                          ctx->d_ctl, ctx->nbatch, ctx->it_done, (int)kOutPartial, (int)kOutDoubles, ctx->d_ticket, ctx->h_out_dev, fuse,
-                         ctx->scale);
-    else
-      hipLaunchKernelGGL(k_reduce, dim3(grid), dim3(kBlock), lds, ctx->stream, ctx->d_traj, ctx->d_px, ctx->d_py,
-                         (int)ctx->P, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
-                         ctx->cfg.safety_hor, ctx->cfg.weight_p, ctx->d_block_partials, ctx->d_nonfinite, ctx->d_out,
-                         ctx->d_ctl, ctx->nbatch, ctx->it_done, (int)kOutPartial, (int)kOutDoubles, ctx->d_ticket, ctx->h_out_dev, fuse);
+                         scl...);
+    });
     if (svsdf_launch_rec *r = record_launch(ctx, ctx->scaled ? SVSDF_KERNEL_REDUCE_SCALED : SVSDF_KERNEL_REDUCE, -1, grid, (unsigned)kBlock, lds,
                                             (long long)ctx->P, 0)) r->fused = fuse;
     if (!fuse) {

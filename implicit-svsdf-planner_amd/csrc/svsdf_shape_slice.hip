@@ -1,8 +1,11 @@
 // svsdf_shape_slice.hip -- one slice of the shape-templated kernels (compile with -DSVSDF_SLICE=k, k = 0 .. 3).
 //
-// Slice k instantiates k_solve / k_round / k_classify / k_rbound / k_subsw / k_shape_kernels / k_succ for the shapes with
-// id % 4 == k and exports the launchers svsdf_pipeline.hip dispatches to (svsdf_launch.hpp).  Splitting the ~250 kernel
-// instantiations over four translation units lets the build run in parallel (one TU took 140 s).
+// Slice k instantiates k_solve / k_round / k_tail / k_classify / k_rbound / k_subsw / k_shape_kernels / k_succ /
+// k_debug_sdf_at for the shapes with id % 4 == k and exports the launchers svsdf_pipeline.hip dispatches to
+// (svsdf_launch.hpp).  k_solve, k_classify and k_debug_sdf_at are each one template with a rigid and a scaled instantiation
+// (an empty parameter pack or ScaleDev, svsdf_kernels.hpp ScaleArg); with_scale picks between them at the one place each is
+// launched.  Splitting the ~580 kernel instantiations over four translation units lets the build run in parallel (one TU
+// took 140 s).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,34 +41,31 @@ bool solve_s(int G, unsigned grid, unsigned block, size_t lds, hipStream_t st, c
   if constexpr (!kernel_shape_enabled<S>()) {
     return false;
   } else {
-    if (a.scl) {   // the scaled path (§4c): widths kScaledLanes only
-#define SOLVE_SC(GG)                                                                                                 \
-  hipLaunchKernelGGL((k_solve_sc<S, GG, 1>), dim3(grid), dim3(block), lds, st, a.traj, a.tk, a.pose, a.chunks, a.sp, \
-                     a.qs, a.out_sdf, a.out_t, a.prune, a.ctl, a.work_idx, a.cull_thresh, a.rot, a.slack_max, *a.scl, a.ltab)
-      switch (G) {
-        case 32: SOLVE_SC(32); break;
-        case 8: SOLVE_SC(8); break;
-        case 4: SOLVE_SC(4); break;
-        default: return false;
-      }
-#undef SOLVE_SC
-      return true;
-    }
-#define SOLVE(GG)                                                                                                   \
-  hipLaunchKernelGGL((k_solve<S, GG, 1>), dim3(grid), dim3(block), lds, st, a.traj, a.tk, a.pose, a.chunks, a.sp,    \
-                     a.qs, a.out_sdf, a.out_t, a.prune, a.ctl, a.work_idx, a.cull_thresh, a.rot, a.slack_max, a.ltab)
     // G lanes per query (G candidates / samples per step); the U = 2 interleaving (two evaluations per lane) was
     // measured and dropped, only U = 1 is instantiated
-    switch (G) {
-      case 1: SOLVE(1); break;
-      case 2: SOLVE(2); break;
-      case 8: SOLVE(8); break;
-      case 16: SOLVE(16); break;
-      case 32: SOLVE(32); break;
-      default: SOLVE(4); break;
-    }
+    return with_scale(a.scl, [&](auto... scl) {
+#define SOLVE(GG)                                                                                                        \
+  hipLaunchKernelGGL((k_solve<S, GG, 1, decltype(scl)...>), dim3(grid), dim3(block), lds, st, a.traj, a.tk, a.pose,      \
+                     a.chunks, a.sp, a.qs, a.out_sdf, a.out_t, a.prune, a.ctl, a.work_idx, a.cull_thresh, a.rot,         \
+                     a.slack_max, scl..., a.ltab)
+      switch (G) {
+        case 32: SOLVE(32); return true;
+        case 8: SOLVE(8); return true;
+        case 4: SOLVE(4); return true;
+      }
+      if constexpr (sizeof...(scl) != 0) {   // the scaled path (§4c): widths kScaledLanes only
+        return false;
+      } else {
+        switch (G) {
+          case 1: SOLVE(1); break;
+          case 2: SOLVE(2); break;
+          case 16: SOLVE(16); break;
+          default: SOLVE(4); break;
+        }
+        return true;
+      }
 #undef SOLVE
-    return true;
+    });
   }
 }
 
@@ -110,12 +110,10 @@ bool classify_s(unsigned grid, size_t lds, hipStream_t st, const ClassifyLaunch 
   if constexpr (!shape_enabled<S>()) {
     return false;
   } else {
-    if (a.scl)
-      hipLaunchKernelGGL((k_classify_sc<S>), dim3(grid), dim3(kBlock), lds, st, a.traj, a.sp, a.px, a.py, a.sdf, a.t,
-                         a.res_sdf, a.res_t, a.res_gx, a.res_gy, a.gs, a.ctl, a.n_int, a.icap, *a.scl);
-    else
-      hipLaunchKernelGGL((k_classify<S>), dim3(grid), dim3(kBlock), lds, st, a.traj, a.sp, a.px, a.py, a.sdf, a.t,
-                         a.res_sdf, a.res_t, a.res_gx, a.res_gy, a.gs, a.ctl, a.n_int, a.icap);
+    with_scale(a.scl, [&](auto... scl) {
+      hipLaunchKernelGGL((k_classify<S, decltype(scl)...>), dim3(grid), dim3(kBlock), lds, st, a.traj, a.sp, a.px, a.py, a.sdf,
+                         a.t, a.res_sdf, a.res_t, a.res_gx, a.res_gy, a.gs, a.ctl, a.n_int, a.icap, scl...);
+    });
     return true;
   }
 }
@@ -165,12 +163,13 @@ bool succ_s(unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm
 
 template <int S>
 bool debug_sdf_at_s(unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp, const double *pxy,
-                    const double *t, int n, double *out, const ScaleDev *scl) {
+                    const double *t, int n, double *out, const ScaleDev *scale) {
   if constexpr (!shape_enabled<S>()) {
     return false;
   } else {
-    if (scl) hipLaunchKernelGGL((k_debug_sdf_at_sc<S>), dim3(grid), dim3(64), lds, st, traj, sp, pxy, t, n, out, *scl);
-    else hipLaunchKernelGGL((k_debug_sdf_at<S>), dim3(grid), dim3(64), lds, st, traj, sp, pxy, t, n, out);
+    with_scale(scale, [&](auto... scl) {
+      hipLaunchKernelGGL((k_debug_sdf_at<S, decltype(scl)...>), dim3(grid), dim3(64), lds, st, traj, sp, pxy, t, n, out, scl...);
+    });
     return true;
   }
 }

@@ -472,9 +472,9 @@ enum svsdf_kernel_kind {
   SVSDF_KERNEL_FINAL = 6,     /* k_final: fixed-order sum of the block partials */
   SVSDF_KERNEL_FINISH = 7,    /* k_finish: suffix sum and counters */
   /* the scaled path (svsdf_set_scale): the launches that run S(t) arithmetic */
-  SVSDF_KERNEL_SOLVE_SCALED = 8,     /* k_solve_sc<shape, G>: rigid scan, scaled descent; G in {4, 8, 32} */
-  SVSDF_KERNEL_CLASSIFY_SCALED = 9,  /* k_classify_sc<shape>: exterior gradient at the scaled body-frame point */
-  SVSDF_KERNEL_REDUCE_SCALED = 10,   /* k_reduce_sc: assembly with the position gradient under S(t*) */
+  SVSDF_KERNEL_SOLVE_SCALED = 8,     /* k_solve<shape, G, 1, ScaleDev>: rigid scan, scaled descent; G in {4, 8, 32} */
+  SVSDF_KERNEL_CLASSIFY_SCALED = 9,  /* k_classify<shape, ScaleDev>: exterior gradient at the scaled body-frame point */
+  SVSDF_KERNEL_REDUCE_SCALED = 10,   /* k_reduce<ScaleDev>: assembly with the position gradient under S(t*) */
   SVSDF_KERNEL_LAYER_TABLES = 11     /* k_layer_tables: pose tables of scan layers 2 / 3 (targ[0]: 2 or 3; only when the plan builds them) */
 };
 typedef struct svsdf_launch_rec {

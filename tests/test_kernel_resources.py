@@ -28,7 +28,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TARGET = b"hipv4-amdgcn-amd-amdhsa--gfx950"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
-NAME_RE = re.compile(r"(k_solve|k_round|k_tail|k_classify)I((?:Li\d+E)+)")
+# the rigid instantiations only: k_solve and k_classify end in a parameter pack that is empty (JE) for the rigid kernel and
+# holds ScaleDev for the scaled one (tests/test_scale_schedule.py has those)
+NAME_RE = re.compile(r"(k_solve|k_round|k_tail|k_classify)I((?:Li\d+E)+)(?:JE)?E")
 
 # Ceilings of today's build, kernel by kernel: shape id -> (scratch bytes per lane, spilled VGPRs) for MODE 0 .. 3 of
 # k_tail<S, MODE, 3>, and for G = 1, 2, 4, 8, 16, 32 of k_solve<S, G, 1>.  Shape 17 is the Polygon with its edges in LDS.

@@ -232,8 +232,9 @@ def _kr():
     return mod
 
 
-SCALED_RE = re.compile(r"(k_solve_sc|k_classify_sc|k_debug_sdf_at_sc|k_round_sc|k_tail_sc)I((?:Li\d+E)+)")
-# k_solve_sc<S, G, 1>, G = 4, 8, 32: (scratch bytes per lane, spilled VGPRs) of today's build
+# a scaled kernel is the instantiation whose trailing template parameter pack holds ScaleDev (rigid: an empty pack or none)
+SCALED_RE = re.compile(r"(k_solve|k_classify|k_debug_sdf_at|k_round|k_tail)I((?:Li\d+E)+)JNS_8ScaleDevEE")
+# k_solve<S, G, 1, ScaleDev>, G = 4, 8, 32: (scratch bytes per lane, spilled VGPRs) of today's build
 SOLVE_SC_CEIL = {s: {4: (0, 0), 8: (0, 0), 32: (0, 0)} for s in range(16)}
 SOLVE_SC_CEIL[16] = {4: (44, 14), 8: (44, 14), 32: (44, 14)}   # (the Polygon: like its rigid k_solve, a few spilled VGPRs)
 SOLVE_SC_CEIL[17] = {4: (52, 16), 8: (52, 16), 32: (52, 16)}
@@ -251,33 +252,33 @@ def scaled_kernels():
                 key = (m.group(1),) + tuple(int(a) for a in re.findall(r"Li(\d+)E", m.group(2)))
                 res[key] = {"scratch": int(k["private_segment_fixed_size"]), "spill": int(k.get("vgpr_spill_count", 0))}
         for k in kr._kernel_notes(co):
-            if k.get("name", "").startswith("_ZN5svsdf11k_reduce_sc"):
-                res[("k_reduce_sc",)] = {"scratch": int(k["private_segment_fixed_size"]), "spill": 0}
+            if k.get("name", "").startswith("_ZN5svsdf8k_reduceIJNS_8ScaleDevEE"):
+                res[("k_reduce",)] = {"scratch": int(k["private_segment_fixed_size"]), "spill": 0}
     return res
 
 
 def test_every_shape_id_has_scaled_kernels(scaled_kernels):
-    """18 compiled shape ids (17 = the Polygon with its edges in LDS) x k_solve_sc<S, G, 1> for G = 4, 8, 32; k_classify_sc
-    and k_debug_sdf_at_sc for the 17 shapes; one k_reduce_sc."""
+    """18 compiled shape ids (17 = the Polygon with its edges in LDS) x k_solve<S, G, 1, ScaleDev> for G = 4, 8, 32;
+    k_classify<S, ScaleDev> and k_debug_sdf_at<S, ScaleDev> for the 17 shapes; one k_reduce<ScaleDev>."""
     for s in range(18):
         for g in (4, 8, 32):
-            assert ("k_solve_sc", s, g, 1) in scaled_kernels, (s, g)
+            assert ("k_solve", s, g, 1) in scaled_kernels, (s, g)
     for s in range(17):
-        assert ("k_classify_sc", s) in scaled_kernels, s
-        assert ("k_debug_sdf_at_sc", s) in scaled_kernels, s
-    assert ("k_reduce_sc",) in scaled_kernels
+        assert ("k_classify", s) in scaled_kernels, s
+        assert ("k_debug_sdf_at", s) in scaled_kernels, s
+    assert ("k_reduce",) in scaled_kernels
 
 
 def test_no_scaled_round_kernel_and_no_new_scratch(scaled_kernels):
     """The scaled path runs the launch chain with the rigid k_round (its GSIP rounds do no S(t) arithmetic): no round-type
     scaled kernel exists, so none can have scratch.  The scaled solves stay at today's scratch and spill counts."""
-    assert not [k for k in scaled_kernels if k[0] in ("k_round_sc", "k_tail_sc")]
+    assert not [k for k in scaled_kernels if k[0] in ("k_round", "k_tail")]
     bad = []
     for (fam, *args), v in scaled_kernels.items():
-        if fam == "k_solve_sc":
+        if fam == "k_solve":
             cs, cv = SOLVE_SC_CEIL[args[0]][args[1]]
             if v["scratch"] > cs or v["spill"] > cv:
-                bad.append(f"k_solve_sc<{args[0]}, {args[1]}>: {v['scratch']} B, {v['spill']} spilled (ceiling {cs}, {cv})")
-        elif fam in ("k_classify_sc", "k_debug_sdf_at_sc", "k_reduce_sc") and v["scratch"] > 0:
+                bad.append(f"k_solve<{args[0]}, {args[1]}, 1, ScaleDev>: {v['scratch']} B, {v['spill']} spilled (ceiling {cs}, {cv})")
+        elif fam in ("k_classify", "k_debug_sdf_at", "k_reduce") and v["scratch"] > 0:
             bad.append(f"{fam}{tuple(args)}: {v['scratch']} B")
     assert not bad, "; ".join(bad)
