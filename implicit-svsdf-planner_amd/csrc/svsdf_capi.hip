@@ -438,6 +438,12 @@ long long svsdf_debug_sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, in
   return sincos_mismatches(ctx, lo, hi, n);
 }
 
+long long svsdf_debug_sqrt_mismatches(svsdf_ctx *ctx, const double *x, size_t n, int flavour) {
+  if (!ctx || ctx->host_only || !x || n == 0 || n > ((size_t)1 << 28) || (flavour != 0 && flavour != 1)) return -1;
+  if (!ctx->subs.empty()) return svsdf_debug_sqrt_mismatches(ctx->subs[0], x, n, flavour);
+  return sqrt_mismatches(ctx, x, n, flavour);
+}
+
 #ifdef SVSDF_SITE_STATS
 // diagnostic builds only (tools/site_stats.py): k_solve's per-site execution / lane counters of the last evaluation
 int svsdf_debug_site_stats(svsdf_ctx *ctx, unsigned long long out[26]) {

@@ -289,6 +289,17 @@ __global__ void k_sincos_check(double lo, double hi, int n, unsigned long long *
     atomicAdd(mism, 1ull);
 }
 
+// operands for which sqrt_nz (flavour 0) / sqrt_z (flavour 1) differs from sqrt in any bit (svsdf_debug_sqrt_mismatches).
+// A wave takes the helper's fast path only when all 64 of its operands are in range: the caller lays the operands out.
+__global__ void k_sqrt_check(const double *__restrict__ x, long long n, int flavour, unsigned long long *mism) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double a = x[i];
+  const double r0 = sqrt(a);
+  const double r1 = flavour ? sqrt_z(a) : sqrt_nz(a);
+  if (__double_as_longlong(r0) != __double_as_longlong(r1)) atomicAdd(mism, 1ull);
+}
+
 #endif  // SVSDF_API_TU
 
 // per-lane cache of the current piece and its [S_lo, S_hi] interval (avoids the LDS walk when
@@ -892,7 +903,7 @@ __device__ __forceinline__ void scan_layer1(const ShapeParams &sp, const Pose *p
     if constexpr (!LITE) {
       if (rot) {   // second exact cull (round 4), see below: the chunk's table minimum less its continuous-path allowance
         const Chunk ch = chunks[c];
-        vbound = dmin(vbound, d_loc - (ch.slack + rot[c] * (norm2(px - ch.cx, py - ch.cy) + ch.rb)));
+        vbound = dmin(vbound, d_loc - (ch.slack + rot[c] * (norm2_s<SHAPE>(px - ch.cx, py - ch.cy) + ch.rb)));
       }
     }
   };
@@ -970,7 +981,7 @@ __device__ __forceinline__ void scan_layer1(const ShapeParams &sp, const Pose *p
             const Pose p = pose[ka];
             const double ax = px - p.x, ay = py - p.y;
             // (the allowance before the evaluation: one number is live across it instead of the anchor's record and position)
-            const double allow = an.adx + sqrt(an.rot2 * (ax * ax + ay * ay)) * (1.0 + 1e-12);
+            const double allow = an.adx + sqrt_s<SHAPE>(an.rot2 * (ax * ax + ay * ay)) * (1.0 + 1e-12);
             da = sdf_from_pose<SHAPE>(sp, p, px, py);
             ++n_scan;
             if (da < d_lane || (da == d_lane && ka < k_lane)) { d_lane = da; k_lane = ka; }
@@ -1025,7 +1036,7 @@ __device__ __forceinline__ void scan_layer1(const ShapeParams &sp, const Pose *p
     int c_loc = 0;
     for (int c = li; c < nch; c += G) {
       const Chunk ch = chunks[c];
-      const double lb = norm2(px - ch.cx, py - ch.cy) - ch.rb;
+      const double lb = norm2_s<SHAPE>(px - ch.cx, py - ch.cy) - ch.rb;
       if (lb < lb_loc) { lb_loc = lb; c_loc = c; }
       lbc_loc = dmin(lbc_loc, lb - ch.slack);
     }
@@ -1049,7 +1060,7 @@ __device__ __forceinline__ void scan_layer1(const ShapeParams &sp, const Pose *p
       bool need = false;
       if (cc < nch && cc != c0) {
         const Chunk ch = chunks[cc];
-        const double lb = norm2(px - ch.cx, py - ch.cy) - ch.rb;
+        const double lb = norm2_s<SHAPE>(px - ch.cx, py - ch.cy) - ch.rb;
         need = !(lb > best_d);
       }
       const unsigned m = Grp<G>::ballot(need);
@@ -2022,7 +2033,7 @@ __device__ __forceinline__ void round_point(const ShapeParams &sp, const Pose *p
         double u = 1e300;
         for (int c = l; c < nch; c += LP) {
           const Chunk ch = chunks[c];
-          u = dmin(u, norm2(cx - ch.cx, cy - ch.cy) + ch.rb);
+          u = dmin(u, norm2_s<SHAPE>(cx - ch.cx, cy - ch.cy) + ch.rb);
         }
         u = dmin(u, Grp<LP>::template xchg<0>(u));
         u = dmin(u, Grp<LP>::template xchg<1>(u));
@@ -2041,7 +2052,7 @@ __device__ __forceinline__ void round_point(const ShapeParams &sp, const Pose *p
           bool keep = false;
           if (c < nch) {
             const Chunk ch = chunks[c];
-            keep = (norm2(cx - ch.cx, cy - ch.cy) - ra) - ch.rb <= thr;
+            keep = (norm2_s<SHAPE>(cx - ch.cx, cy - ch.cy) - ra) - ch.rb <= thr;
           }
           const unsigned mk = ballot_g(keep);
           const int pos = cnt + __popc(mk & lt_mask);
@@ -2196,8 +2207,8 @@ __device__ __forceinline__ void round_point(const ShapeParams &sp, const Pose *p
               const double ur = __shfl(ub[ps], rsrc, LP), xr = __shfl(sqx_l[ps], rsrc, LP), yr = __shfl(sqy_l[ps], rsrc, LP);
               const bool rv = __shfl((int)(valid[ps] && scanned[ps]), rsrc, LP) != 0;
               if (valid[ps] && !scanned[ps]) {
-                double b = ul + norm2(sqx_l[ps] - xl, sqy_l[ps] - yl);
-                if (rv) b = dmin(b, ur + norm2(sqx_l[ps] - xr, sqy_l[ps] - yr));
+                double b = ul + norm2_s<SHAPE>(sqx_l[ps] - xl, sqy_l[ps] - yl);
+                if (rv) b = dmin(b, ur + norm2_s<SHAPE>(sqx_l[ps] - xr, sqy_l[ps] - yr));
                 ub[ps] = b + 1e-9;
               }
             }

@@ -1340,4 +1340,22 @@ long long sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, int n) {
   return (long long)h;
 }
 
+// mismatch count of the kernels' unscaled sqrt against sqrt on n host operands (svsdf_debug_sqrt_mismatches)
+long long sqrt_mismatches(svsdf_ctx *ctx, const double *x, size_t n, int flavour) {
+  if (hipSetDevice(ctx->device) != hipSuccess) return -1;
+  double *dx = nullptr;
+  if (hipMalloc(&dx, n * sizeof(double)) != hipSuccess) return -1;
+  unsigned long long *d = reinterpret_cast<unsigned long long *>(ctx->d_out);
+  unsigned long long h = 0;
+  bool ok = hipMemcpyAsync(dx, x, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
+            hipMemsetAsync(d, 0, sizeof(unsigned long long), ctx->stream) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_sqrt_check, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, dx, (long long)n, flavour, d);
+    ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+  }
+  ok = (hipStreamSynchronize(ctx->stream) == hipSuccess) && ok;
+  ok = (hipFree(dx) == hipSuccess) && ok;
+  return ok ? (long long)h : -1;
+}
+
 }  // namespace svsdf_impl

@@ -79,7 +79,77 @@ __device__ __forceinline__ double div_const(double a, double b, double rb) {
   return a / b;
 #endif
 }
-__device__ __forceinline__ double norm2(double x, double y) { return sqrt(x * x + y * y); }
+
+// sqrt(x) without the range scaling (round 8).  The compiler expands a double sqrt into v_rsq_f64 and nine multiply / fma
+// steps (Goldschmidt), wrapped in a range scaling that only acts on radicands below 2^-767 (compare, two selects, ldexp by
+// 256 in and by -128 out) and a class test that hands +-0 and +inf through (compare, two selects): 18 instructions, 8 of
+// them for operands no distance here ever takes.  sqrt_core is the same sequence, operation for operation, with both
+// ldexp exponents zero -- for 2^-767 <= x < inf the bits are the expansion's by construction.  Everything else takes
+// sqrt(x) itself, wave-uniformly (like div_const): when ANY active lane holds such an operand, the whole wave does.
+// A NaN takes the slow path and yields NaN there (it would on the fast one too: rsq(NaN) = NaN runs through every step).
+//   sqrt_nz   radicands that are essentially never zero (|q| of a body-frame point, chunk / anchor distances, a distance
+//             to a segment): one integer range test on the high word, 2^-767 <= x < inf, is the whole guard; zeros, inf,
+//             NaN, tiny and negative operands all leave through sqrt(x).  12 instructions.
+//   sqrt_z    radicands that are often exactly +0 (sdHorseshoe's norm2(max(nx, 0), max(ny, 0)): every interior point):
+//             +0 stays on the fast path -- rsq(+0) = +inf is clamped to 2^1023, which no in-range operand reaches
+//             (rsq <= 2^384), and the sequence then carries g = 0 * 2^1023 = +0 through to the result.  -0 (never produced
+//             by a sum of squares, but an operand like any other) has the high word 0x80000000: out of range, non-zero
+//             bits, slow path.  14 instructions.
+// The empty asm in the slow branch keeps the compiler from if-converting it (it otherwise computes BOTH expansions and
+// selects).  tests/test_sqrt_unscaled_gpu.py holds both against sqrt on ~2 M operands (svsdf_debug_sqrt_mismatches).
+#ifndef SVSDF_SQRT_UNSCALED
+#define SVSDF_SQRT_UNSCALED 1
+#endif
+#if SVSDF_SQRT_UNSCALED && defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ double sqrt_core(double x, double y /* rsq(x) */) {
+  double g = x * y;
+  double h = 0.5 * y;
+  const double r = __builtin_fma(-h, g, 0.5);
+  g = __builtin_fma(g, r, g);
+  h = __builtin_fma(h, r, h);
+  double d = __builtin_fma(-g, g, x);
+  g = __builtin_fma(d, h, g);
+  d = __builtin_fma(-g, g, x);
+  return __builtin_fma(d, h, g);
+}
+// high word in [0x10000000, 0x7ff00000): 2^-767 <= x < +inf
+__device__ __forceinline__ bool sqrt_in_range(double x) { return (unsigned)__double2hiint(x) - 0x10000000u < 0x6ff00000u; }
+__device__ __forceinline__ double sqrt_nz(double x) {
+  double g = sqrt_core(x, __builtin_amdgcn_rsq(x));
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!sqrt_in_range(x)) != 0ull, 0)) {
+    asm volatile("" : "+v"(x));
+    g = sqrt(x);
+  }
+  return g;
+}
+__device__ __forceinline__ double sqrt_z(double x) {
+  double g = sqrt_core(x, __builtin_fmin(__builtin_amdgcn_rsq(x), 0x1p1023));
+  const unsigned long long slow = __builtin_amdgcn_ballot_w64(!sqrt_in_range(x)) &
+                                  __builtin_amdgcn_ballot_w64(__double_as_longlong(x) != 0ll);
+  if (__builtin_expect(slow != 0ull, 0)) {
+    asm volatile("" : "+v"(x));
+    g = sqrt(x);
+  }
+  return g;
+}
+#else
+__device__ __forceinline__ double sqrt_nz(double x) { return sqrt(x); }
+__device__ __forceinline__ double sqrt_z(double x) { return sqrt(x); }
+#endif
+__device__ __forceinline__ double norm2(double x, double y) { return sqrt_nz(x * x + y * y); }     // essentially never zero
+__device__ __forceinline__ double norm2_z(double x, double y) { return sqrt_z(x * x + y * y); }    // often exactly zero
+// Kernels that keep sqrt: the Polygon instantiations sit at their register cap (k_tail<Polygon, 0, 3> gained 4 B of scratch
+// and 7 spilled registers with the helpers in the chunk bounds) and k_tail<sdArc, 0, 3> gained two spilled registers
+// (tests/test_kernel_resources.py holds every kernel at its bytes).  Their shape formulas (svsdf_polygon.hpp, sdf_arc) and
+// the chunk / anchor distances of their kernels (norm2_s / sqrt_s<SHAPE>: never-zero flavour elsewhere) are as they were.
+template <int SHAPE>
+constexpr bool keeps_sqrt() { return SHAPE == kPolygon || SHAPE == kPolygonLds || SHAPE == kArc; }
+template <int SHAPE>
+__device__ __forceinline__ double sqrt_s(double x) {
+  if constexpr (keeps_sqrt<SHAPE>()) return sqrt(x); else return sqrt_nz(x);
+}
+template <int SHAPE>
+__device__ __forceinline__ double norm2_s(double x, double y) { return sqrt_s<SHAPE>(x * x + y * y); }
 
 // SHP:531-543
 __device__ __forceinline__ double sdf_uneven_capsule(double px, double py) {
@@ -114,7 +184,7 @@ __device__ __forceinline__ double sdf_trapezoid(double px, double py) {
   const double cbx = (px - k1x) + k2x * c;
   const double cby = (py - k1y) + k2y * c;
   const double s = (cbx < 0.0 && cay < 0.0) ? -1.0 : 1.0;
-  return s * sqrt(dmin(cax * cax + cay * cay, cbx * cbx + cby * cby));
+  return s * sqrt_nz(dmin(cax * cax + cay * cay, cbx * cbx + cby * cby));
 }
 
 // SHP:809-826
@@ -164,10 +234,10 @@ __device__ __forceinline__ double sdf_tunnel(double px, double py) {
   const double qy = py - why;
   const double m = dmax(qx, 0.0);
   const double d1 = m * m + qy * qy;
-  qx = (py > 0.0) ? qx : sqrt(px * px + py * py) - whx;
+  qx = (py > 0.0) ? qx : sqrt_nz(px * px + py * py) - whx;
   const double n = dmax(qy, 0.0);
   const double d2 = qx * qx + n * n;
-  const double d = sqrt(dmin(d1, d2));
+  const double d = sqrt_nz(dmin(d1, d2));
   return (dmax(qx, qy) < 0.0) ? -d : d;
 }
 
@@ -183,7 +253,7 @@ __device__ __forceinline__ double sdf_horseshoe(double px, double py, double cx,
   if (pxr <= 0) ny = l;
   nx = nx - wx;
   ny = fabs(ny - r) - wy;
-  return norm2(dmax(nx, 0.0), dmax(ny, 0.0)) + dmin(0.0, dmax(nx, ny));
+  return norm2_z(dmax(nx, 0.0), dmax(ny, 0.0)) + dmin(0.0, dmax(nx, ny));   // +0 for every interior point
 }
 
 // SHP:939-952
@@ -193,14 +263,14 @@ __device__ __forceinline__ double sdf_heart(double px, double py) {
   px = fabs(px);
   if (py + px > 1.0) {
     const double ax = px - 0.25, ay = py - 0.75;
-    return 4 * (sqrt(ax * ax + ay * ay) - sqrt(2.0) / 4.0);
+    return 4 * (sqrt_nz(ax * ax + ay * ay) - sqrt(2.0) / 4.0);
   }
   const double bx = px - 0.0, by = py - 1.0;
   const double value1 = bx * bx + by * by;
   const double temp = dmax(px + py, 0.0);
   const double cx = px - 0.5 * temp, cy = py - 0.5 * temp;
   const double value2 = cx * cx + cy * cy;
-  return 4 * (sqrt(dmin(value1, value2)) * copysign(1.0, px - py));
+  return 4 * (sqrt_nz(dmin(value1, value2)) * copysign(1.0, px - py));
 }
 
 // SHP:988-994 (w = 3) and SHP:1024-1030 (bigX, w = 5)
@@ -220,18 +290,18 @@ __device__ __forceinline__ double sdf_rounded_cross(double px, double py) {
   const double ax = fabs(px), ay = fabs(py);
   if (ax < 1.0 && ay < ax * (k - h) + h) {
     const double ux = ax - 1, uy = ay - k;
-    return 2 * (k - sqrt(ux * ux + uy * uy));
+    return 2 * (k - sqrt_nz(ux * ux + uy * uy));
   } else {
     const double ux = ax - 0, uy = ay - h;
     const double vx = ax - 1, vy = ay - 0;
-    return 2 * sqrt(dmin(ux * ux + uy * uy, vx * vx + vy * vy));
+    return 2 * sqrt_nz(dmin(ux * ux + uy * uy, vx * vx + vy * vy));
   }
 }
 
 // SHP:1115-1146
 __device__ __forceinline__ double sdf_oriented_vesica(double px, double py) {
   const double ax = 2, ay = 4, bx = -2, by = -4, w = 0.8;
-  const double r = 0.5 * norm2(bx - ax, by - ay);
+  const double r = 0.5 * sqrt((bx - ax) * (bx - ax) + (by - ay) * (by - ay));   // a constant: folded at compile time
   const double d = 0.5 * (r * r - w * w) / w;
   const double vx = (bx - ax) / r, vy = (by - ay) / r;
   const double cx = 0.5 * (bx + ax), cy = 0.5 * (by + ay);
@@ -271,8 +341,8 @@ __device__ __forceinline__ double sdf_arc(double px, double py, double scx, doub
   const double ra = 2.3333, rb = 0.5;
   px = fabs(px);
   const bool condition = scy * px > scx * py;
-  const double dist1 = norm2(px - scx * ra, py - scy * ra);
-  const double dist2 = fabs(norm2(px, py) - ra);
+  const double dist1 = norm2_s<kArc>(px - scx * ra, py - scy * ra);   // (keeps sqrt: keeps_sqrt)
+  const double dist2 = fabs(norm2_s<kArc>(px, py) - ra);
   return (condition ? dist1 : dist2) - rb;
 }
 

@@ -23,7 +23,7 @@ EXPORTS = [
     "svsdf_accumulate_partial", "svsdf_lmbm_evaluate", "svsdf_last_costs", "svsdf_lmbm_begin",
     "svsdf_lmbm_finish", "svsdf_minco_coeffs", "svsdf_forward_T", "svsdf_backward_T",
     "svsdf_query_points", "svsdf_last_stats", "svsdf_shard_indices", "svsdf_set_profiling",
-    "svsdf_shard_plan", "svsdf_lmbm_prepare", "svsdf_debug_sincos_mismatches",
+    "svsdf_shard_plan", "svsdf_lmbm_prepare", "svsdf_debug_sincos_mismatches", "svsdf_debug_sqrt_mismatches",
     "svsdf_map_create", "svsdf_map_destroy", "svsdf_map_info", "svsdf_map_gather", "svsdf_pcd_read_ascii",
     "svsdf_check_sub_sw_collision", "svsdf_shape_kernels",
     "svsdf_lbfgs_params_default", "svsdf_lbfgs_minimize", "svsdf_optimize_traj",
@@ -181,6 +181,8 @@ def lib():
     L.svsdf_pcd_read_ascii.argtypes = [C.c_char_p, _fp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.svsdf_debug_sincos_mismatches.restype = C.c_longlong
     L.svsdf_debug_sincos_mismatches.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int]
+    L.svsdf_debug_sqrt_mismatches.restype = C.c_longlong
+    L.svsdf_debug_sqrt_mismatches.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_int]
     L.svsdf_lbfgs_params_default.argtypes = [C.POINTER(LbfgsParams)]
     L.svsdf_lbfgs_params_default.restype = None
     _ip = C.POINTER(C.c_int)
@@ -744,6 +746,11 @@ class SvsdfContext:
 
     def sincos_mismatches(self, lo, hi, n):
         return int(self.L.svsdf_debug_sincos_mismatches(self.ctx, float(lo), float(hi), int(n)))
+
+    def sqrt_mismatches(self, x, flavour):
+        """Operands of x (float64 bit patterns kept as given) whose unscaled device sqrt differs from sqrt; flavour 0 / 1."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        return int(self.L.svsdf_debug_sqrt_mismatches(self.ctx, _p(x), x.size, int(flavour)))
 
     def shape_bound(self):
         """(analytic R with sdf(q) >= |q| - R, largest |q| - sdf(q) sampled at creation)."""

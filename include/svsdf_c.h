@@ -593,6 +593,11 @@ int svsdf_set_profiling(svsdf_ctx *ctx, int enable);
 /* Self-check: number of n equispaced arguments in [lo, hi] for which the kernels' inlined sincos
  * differs by even one bit from the ROCm device library's sincos (must be 0); -1 on error. */
 long long svsdf_debug_sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, int n);
+/* Self-check: number of the n operands x for which the kernels' square root without range scaling differs by even one
+ * bit from sqrt (must be 0); -1 on error.  flavour 0: the helper for radicands that are never zero, 1: the one that keeps
+ * +0 on its fast path.  The helpers decide per wave of 64 consecutive operands: one operand outside [2^-767, inf) sends
+ * its whole wave through sqrt itself, so a caller that wants the fast path exercised keeps such operands apart. */
+long long svsdf_debug_sqrt_mismatches(svsdf_ctx *ctx, const double *x, size_t n, int flavour);
 /* Diagnostic / test: getSDFAtTimeStamp<false> (sw_manager.hpp:741-750) of n (point, time) pairs on the device, through
  * the code the solve kernels inline.  points_xy: n x 2, t: n; out8: n x 8 = sdf, pose x, y, cos(yaw), sin(yaw), body-frame
  * x, y of the point, piece-time mode (0 cumulative, 1 / 2 the reference's chain).  Under a scale schedule
