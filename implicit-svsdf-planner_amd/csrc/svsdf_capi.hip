@@ -290,13 +290,14 @@ void svsdf_destroy(svsdf_ctx *ctx) {
                   ctx->gs.sq_ub, ctx->gs.sq_k, ctx->gs.sq_sdf, ctx->gs.sq_t, ctx->d_ctl,
                   ctx->d_block_partials, ctx->d_sums,
                   ctx->d_out, ctx->d_nonfinite, ctx->d_fe, ctx->d_fe_flag, ctx->d_ticket,
-                  ctx->d_fm_occ, ctx->d_fm_free, ctx->d_fm_kt, ctx->d_succ};
+                  ctx->d_fm_occ, ctx->d_fm_free, ctx->d_fm_kt, ctx->d_succ, ctx->d_astar};
   for (void *p : bufs)
     if (p) (void)hipFree(p);
   if (ctx->h_in) (void)hipHostFree(ctx->h_in);
   if (ctx->h_out) (void)hipHostFree(ctx->h_out);
   if (ctx->h_fe) (void)hipHostFree(ctx->h_fe);
   if (ctx->h_succ) (void)hipHostFree(ctx->h_succ);
+  if (ctx->h_astar) (void)hipHostFree(ctx->h_astar);
   for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
   if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);
   for (int b = 0; b < kMaxBatches; ++b)

@@ -208,6 +208,13 @@ struct svsdf_ctx {
   double *d_fm_kt = nullptr;
   unsigned char *d_succ = nullptr, *h_succ = nullptr;
   size_t succ_cap = 0;                        // parents
+  // svsdf_astar_search: one device blob [state | node records | open set | path], carved up in `astar`; sized for the
+  // resident map at the first search on it, released with the map
+  unsigned char *d_astar = nullptr;
+  svsdf::AstarState *h_astar = nullptr;       // pinned: the state goes up once per search and comes back once per launch
+  int fm_Z = 0;                               // layers of the resident map's grid (the search stays in layer 0)
+  svsdf::AstarDev astar{};
+  bool astar_searched = false;                // the node records hold a search on the resident map
 
   // profiling
   bool profile = false;  // per-launch HIP events (env SVSDF_PROFILE=1 or svsdf_set_profiling)

@@ -203,6 +203,11 @@ static void frontend_release(svsdf_ctx *ctx) {
     if (p) (void)hipFree(p);
   ctx->d_fm_occ = ctx->d_fm_free = nullptr;
   ctx->d_fm_kt = nullptr;
+  // the search state belongs to the map
+  if (ctx->d_astar) (void)hipFree(ctx->d_astar);
+  ctx->d_astar = nullptr;
+  ctx->astar = AstarDev{};
+  ctx->astar_searched = false;
 }
 
 int svsdf_frontend_set_map(svsdf_ctx *ctx, const svsdf_map *map, int kernel_size, int kernel_count, double safemargin) {
@@ -287,6 +292,7 @@ int svsdf_frontend_set_map(svsdf_ctx *ctx, const svsdf_map *map, int kernel_size
   fm.res = m.resolution();
   fm.half = (double)(kernel_size / 2 + 1);   // front_end_Astar.hpp:224: integer division, metres
   for (int d = 0; d < 3; ++d) { fm.bmin[d] = m.bmin()[d]; fm.bmax[d] = m.bmax()[d]; }
+  ctx->fm_Z = Z;
   ctx->fm_set = true;
   return SVSDF_OK;
 }
@@ -372,6 +378,184 @@ int svsdf_astar_successors(svsdf_ctx *ctx, size_t n, const int *parent_ij, const
     for (size_t e = 0; e < 9 * m; ++e) ok_out[9 * p0 + e] = hs[e] == 0 ? 1 : 0;
     if (stage_out) std::memcpy(stage_out + 9 * p0, hs, 9 * m);
   }
+  return SVSDF_OK;
+}
+
+// ---- A* search on the resident map ----------------------------------------------------------------------------------
+void svsdf_astar_params_default(svsdf_astar_params *p) {
+  if (!p) return;
+  *p = svsdf_astar_params{};
+  p->struct_size = (int)sizeof(svsdf_astar_params);
+  p->start_yaw = 0.0;   // front_end_Astar.hpp:281
+}
+
+// one device blob: [state | g f yaw | open keys, seqs, path yaws | father, open cells, path cells | id]
+static int astar_alloc(svsdf_ctx *ctx) {
+  if (ctx->d_astar) return SVSDF_OK;
+  const size_t cells = (size_t)ctx->fm.X * ctx->fm.Y, cap = cells + 1;
+  if (cap > 0x7fffffffull) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: map too large");
+  const size_t head = 256;
+  const size_t bytes = head + 8 * (3 * cells + 3 * cap) + 4 * (cells + 2 * cap) + cells;
+  int rc = dev_alloc(ctx, &ctx->d_astar, bytes);
+  if (rc) return rc;
+  if (!ctx->h_astar) HIPCHK(hipHostMalloc((void **)&ctx->h_astar, sizeof(AstarState)));
+  static_assert(sizeof(AstarState) <= 256, "state header");
+  AstarDev &a = ctx->astar;
+  unsigned char *b = ctx->d_astar;
+  a.st = reinterpret_cast<AstarState *>(b);
+  double *d = reinterpret_cast<double *>(b + head);
+  a.g = d; a.f = d + cells; a.yaw = d + 2 * cells;
+  a.okey = d + 3 * cells;
+  a.oseq = reinterpret_cast<unsigned long long *>(d + 3 * cells + cap);
+  a.path_yaw = d + 3 * cells + 2 * cap;
+  int *i4 = reinterpret_cast<int *>(d + 3 * cells + 3 * cap);
+  a.father = i4; a.ocell = i4 + cells; a.path_cell = i4 + cells + cap;
+  a.id = reinterpret_cast<signed char *>(i4 + cells + 2 * cap);
+  a.open_cap = (int)cap;
+  return SVSDF_OK;
+}
+
+// isInMap (Gridmap3D.cpp:43-71)
+static bool astar_in_map(const FrontMapDev &fm, const double p[3]) {
+  for (int d = 0; d < 3; ++d)
+    if (p[d] < fm.bmin[d] || p[d] > fm.bmax[d]) return false;
+  return true;
+}
+// getGridIndex (Gridmap3D.cpp:137-177) of a point inside the map, one axis
+static int astar_axis_index(double p, double bmin, double res, int size) {
+  int i = (int)std::floor((p - bmin) / res);
+  if (i < 0) i = 0;
+  if (i >= size) i = size - 1;
+  return i;
+}
+
+int svsdf_astar_search(svsdf_ctx *ctx, const double start_xyz[3], const double end_xyz[3], const svsdf_astar_params *params,
+                       double *path_xyyaw, int *path_ij, size_t capacity_cells, svsdf_astar_result *result) {
+  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_astar_search: no device context");
+  if (!ctx->subs.empty()) {
+    const int r = svsdf_astar_search(ctx->subs[0], start_xyz, end_xyz, params, path_xyyaw, path_ij, capacity_cells, result);
+    if (r) ctx->err = ctx->subs[0]->err;
+    return r;
+  }
+  if (!ctx->fm_set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: no map (svsdf_frontend_set_map)");
+  if (!start_xyz || !end_xyz || !result) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: null argument");
+  svsdf_astar_params prm;
+  svsdf_astar_params_default(&prm);
+  if (params) {
+    if (params->struct_size != (int)sizeof(svsdf_astar_params))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: params->struct_size is not sizeof(svsdf_astar_params)");
+    prm = *params;
+  }
+  if (result->struct_size != (int)sizeof(svsdf_astar_result))
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: result->struct_size is not sizeof(svsdf_astar_result)");
+  const FrontMapDev &fm = ctx->fm;
+  {
+    double cy;
+    int ki;
+    if (kernel_bfs(0ull, fm.kernel_count, prm.start_yaw, &cy, &ki) < 0)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: start_yaw maps to a kernel index outside [0, kernel_count)");
+  }
+  if (prm.slice < 0) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: slice < 0");
+  if (prm.max_expansions < 0) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: max_expansions < 0");
+  for (int d = 0; d < 3; ++d)
+    if (!std::isfinite(start_xyz[d]) || !std::isfinite(end_xyz[d]))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: start or end not finite");
+  *result = svsdf_astar_result{};
+  result->struct_size = (int)sizeof(svsdf_astar_result);
+  if (!astar_in_map(fm, start_xyz) || !astar_in_map(fm, end_xyz)) {   // front_end_Astar.hpp:249-254
+    result->status = SVSDF_ASTAR_OUT_OF_MAP;
+    return SVSDF_OK;
+  }
+  if (astar_axis_index(start_xyz[2], fm.bmin[2], fm.res, ctx->fm_Z) != 0 || astar_axis_index(end_xyz[2], fm.bmin[2], fm.res, ctx->fm_Z) != 0)
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: the search is planar in layer 0; the z index of start or end is not 0");
+  const int slice = prm.slice ? prm.slice : kAstarDefaultSlice;
+
+  HIPCHK(hipSetDevice(ctx->device));
+  int rc = astar_alloc(ctx);
+  if (rc) return rc;
+  const AstarDev &a = ctx->astar;
+  const size_t cells = (size_t)fm.X * fm.Y;
+  hipStream_t st = ctx->stream;
+  ctx->astar_searched = false;
+  // AstarPathSearcher::reset (:154-163) + the search's own state
+  AstarState *h = ctx->h_astar;
+  *h = AstarState{};
+  h->status = kAstarRunning;
+  h->si = astar_axis_index(start_xyz[0], fm.bmin[0], fm.res, fm.X);
+  h->sj = astar_axis_index(start_xyz[1], fm.bmin[1], fm.res, fm.Y);
+  h->gi = astar_axis_index(end_xyz[0], fm.bmin[0], fm.res, fm.X);
+  h->gj = astar_axis_index(end_xyz[1], fm.bmin[1], fm.res, fm.Y);
+  h->max_expansions = (unsigned long long)prm.max_expansions;
+  h->start_yaw = prm.start_yaw;
+  h->pushes = 1ull;   // the start node's own openSet.insert (:283); the kernel counts the neighbours'
+  HIPCHK(hipMemsetAsync(a.g, 0, 3 * cells * sizeof(double), st));       // g | f | yaw
+  HIPCHK(hipMemsetAsync(a.father, 0xff, cells * sizeof(int), st));      // -1
+  HIPCHK(hipMemsetAsync(a.id, 0, cells, st));
+  HIPCHK(hipMemcpyAsync(a.st, h, sizeof(AstarState), hipMemcpyHostToDevice, st));
+  unsigned long long launches = 0;
+  do {
+    if (!launch_k_astar(ctx->cfg.shape_id, st, ctx->sp, fm, a, slice))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: shape not compiled into this library");
+    HIPCHK(hipGetLastError());
+    ++launches;
+    HIPCHK(hipMemcpyAsync(h, a.st, sizeof(AstarState), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  } while (h->status == kAstarRunning);
+  if (h->status < 0 || h->status > SVSDF_ASTAR_LIMIT)
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: internal error: the open set or the path outgrew X * Y + 1 entries");
+  ctx->astar_searched = true;
+  result->status = h->status;
+  result->path_len = h->status == SVSDF_ASTAR_FOUND ? (size_t)h->path_len : 0;
+  result->expansions = h->expansions; result->pushes = h->pushes; result->relaxed_open = h->relaxed_open;
+  result->reopened = h->reopened; result->launches = launches;
+  for (int k = 0; k < 5; ++k) result->stage_counts[k] = h->stage_counts[k];
+  result->g_goal = h->status == SVSDF_ASTAR_FOUND ? h->g_goal : 0.0;
+  const size_t n = result->path_len;
+  if ((path_xyyaw || path_ij) && n) {
+    if (capacity_cells < n)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: capacity_cells too small (result->path_len cells are needed)");
+    std::vector<int> cell(n);
+    std::vector<double> yaw(n);
+    HIPCHK(hipMemcpyAsync(cell.data(), a.path_cell, n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(yaw.data(), a.path_yaw, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (size_t k = 0; k < n; ++k) {
+      const int i = cell[k] / fm.Y, j = cell[k] - i * fm.Y;
+      if (path_ij) { path_ij[2 * k] = i; path_ij[2 * k + 1] = j; }
+      if (path_xyyaw) {   // getGridCubeCenter (Gridmap3D.cpp:184-195), coord(2) = yaw (:381)
+        path_xyyaw[3 * k] = (i + 0.5) * fm.res + fm.bmin[0];
+        path_xyyaw[3 * k + 1] = (j + 0.5) * fm.res + fm.bmin[1];
+        path_xyyaw[3 * k + 2] = yaw[k];
+      }
+    }
+  }
+  return SVSDF_OK;
+}
+
+int svsdf_astar_nodes(const svsdf_ctx *cctx, signed char *id, double *g, double *f, double *yaw, int *father_cell,
+                      size_t capacity, int dims2[2]) {
+  svsdf_ctx *ctx = const_cast<svsdf_ctx *>(cctx);   // (the error string is the only thing written)
+  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_astar_nodes: no device context");
+  if (!ctx->subs.empty()) {
+    const int r = svsdf_astar_nodes(ctx->subs[0], id, g, f, yaw, father_cell, capacity, dims2);
+    if (r) ctx->err = ctx->subs[0]->err;
+    return r;
+  }
+  if (!ctx->fm_set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_nodes: no map (svsdf_frontend_set_map)");
+  if (dims2) { dims2[0] = ctx->fm.X; dims2[1] = ctx->fm.Y; }
+  if (!id && !g && !f && !yaw && !father_cell) return SVSDF_OK;
+  if (!ctx->astar_searched) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_nodes: no search on this map yet (svsdf_astar_search)");
+  const size_t n = (size_t)ctx->fm.X * ctx->fm.Y;
+  if (capacity < n) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_nodes: capacity too small (query with all pointers NULL first)");
+  const AstarDev &a = ctx->astar;
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (id) HIPCHK(hipMemcpyAsync(id, a.id, n, hipMemcpyDeviceToHost, st));
+  if (g) HIPCHK(hipMemcpyAsync(g, a.g, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (f) HIPCHK(hipMemcpyAsync(f, a.f, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (yaw) HIPCHK(hipMemcpyAsync(yaw, a.yaw, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (father_cell) HIPCHK(hipMemcpyAsync(father_cell, a.father, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
   return SVSDF_OK;
 }
 

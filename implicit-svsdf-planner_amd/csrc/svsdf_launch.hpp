@@ -58,6 +58,7 @@ bool launch_k_debug_sdf_at(int shape, unsigned grid, size_t lds, hipStream_t st,
                            const double *pxy, const double *t, int n, double *out, const ScaleDev *scl = nullptr);
 bool launch_k_succ(int shape, unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const int *parent_ij,
                    const double *parent_yaw, double *yaw_out, unsigned char *stage_out);
+bool launch_k_astar(int shape, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const AstarDev &a, int slice);
 // shape-independent front-end kernels (svsdf_pipeline.hip)
 void launch_k_pack_kernel_rows(hipStream_t st, const unsigned char *map, int ks, int count, unsigned long long *rows);
 void launch_k_yaw_free(hipStream_t st, const unsigned long long *occ, int row_words, const unsigned long long *krows, int ks,
@@ -77,7 +78,8 @@ void launch_k_yaw_free(hipStream_t st, const unsigned long long *occ, int row_wo
   bool launch_k_debug_sdf_at_s##K(int shape, unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp,    \
                                   const double *pxy, const double *t, int n, double *out, const ScaleDev *scl);                 \
   bool launch_k_succ_s##K(int shape, unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm,                      \
-                          const int *parent_ij, const double *parent_yaw, double *yaw_out, unsigned char *stage_out);
+                          const int *parent_ij, const double *parent_yaw, double *yaw_out, unsigned char *stage_out);       \
+  bool launch_k_astar_s##K(int shape, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const AstarDev &a, int slice);
 SVSDF_DECLARE_SLICE(0)
 SVSDF_DECLARE_SLICE(1)
 SVSDF_DECLARE_SLICE(2)

@@ -165,6 +165,10 @@ bool launch_k_succ(int shape, unsigned grid, hipStream_t st, ShapeParams sp, con
   shape = svsdf_impl::compiled_shape(shape);
   SVSDF_SLICE_DISPATCH(launch_k_succ, grid, st, sp, fm, parent_ij, parent_yaw, yaw_out, stage_out)
 }
+bool launch_k_astar(int shape, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const AstarDev &a, int slice) {
+  shape = svsdf_impl::compiled_shape(shape);
+  SVSDF_SLICE_DISPATCH(launch_k_astar, st, sp, fm, a, slice)
+}
 void launch_k_pack_kernel_rows(hipStream_t st, const unsigned char *map, int ks, int count, unsigned long long *rows) {
   hipLaunchKernelGGL(k_pack_kernel_rows, dim3((unsigned)((ks * count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, map, ks,
                      count, rows);

@@ -1,7 +1,7 @@
 // svsdf_shape_slice.hip -- one slice of the shape-templated kernels (compile with -DSVSDF_SLICE=k, k = 0 .. 3).
 //
 // Slice k instantiates k_solve / k_round / k_tail / k_classify / k_rbound / k_subsw / k_shape_kernels / k_succ /
-// k_debug_sdf_at for the shapes with id % 4 == k and exports the launchers svsdf_pipeline.hip dispatches to
+// k_astar / k_debug_sdf_at for the shapes with id % 4 == k and exports the launchers svsdf_pipeline.hip dispatches to
 // (svsdf_launch.hpp).  k_solve, k_classify and k_debug_sdf_at are each one template with a rigid and a scaled instantiation
 // (an empty parameter pack or ScaleDev, svsdf_kernels.hpp ScaleArg); with_scale picks between them at the one place each is
 // launched.  Splitting the ~580 kernel instantiations over four translation units lets the build run in parallel (one TU
@@ -162,6 +162,16 @@ bool succ_s(unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm
 }
 
 template <int S>
+bool astar_s(hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const AstarDev &a, int slice) {
+  if constexpr (!shape_enabled<S>() || is_polygon<S>()) {   // no yaw kernels for the Polygon (shape_kernels_s)
+    return false;
+  } else {
+    hipLaunchKernelGGL((k_astar<S>), dim3(1), dim3(kAstarBlock), 0, st, sp, fm, a, slice);   // one workgroup per search
+    return true;
+  }
+}
+
+template <int S>
 bool debug_sdf_at_s(unsigned grid, size_t lds, hipStream_t st, const TrajDev *traj, ShapeParams sp, const double *pxy,
                     const double *t, int n, double *out, const ScaleDev *scale) {
   if constexpr (!shape_enabled<S>()) {
@@ -232,6 +242,11 @@ bool SLICE_FN(launch_k_shape_kernels)(int shape, unsigned grid, hipStream_t st, 
 bool SLICE_FN(launch_k_succ)(int shape, unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const int *parent_ij,
                              const double *parent_yaw, double *yaw_out, unsigned char *stage_out) {
 #define CALL(S) succ_s<S>(grid, st, sp, fm, parent_ij, parent_yaw, yaw_out, stage_out)
+  SLICE_SWITCH(CALL)
+#undef CALL
+}
+bool SLICE_FN(launch_k_astar)(int shape, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const AstarDev &a, int slice) {
+#define CALL(S) astar_s<S>(st, sp, fm, a, slice)
   SLICE_SWITCH(CALL)
 #undef CALL
 }

@@ -33,6 +33,7 @@ EXPORTS = [
     "svsdf_group_stripe", "svsdf_set_group_serial", "svsdf_shape_selfcheck", "svsdf_mesh_section", "svsdf_mesh_section_obj",
     "svsdf_last_launches", "svsdf_set_scale", "svsdf_get_scale",
     "svsdf_frontend_set_map", "svsdf_frontend_yaw_free", "svsdf_kernel_bfs", "svsdf_astar_successors",
+    "svsdf_astar_params_default", "svsdf_astar_search", "svsdf_astar_nodes",
 ]
 
 
@@ -104,6 +105,21 @@ class Scale(C.Structure):
 
 # the reference's worked example (sw_manager.hpp:498-500): s_x = 0.8 + sin(1.5 t - 1.0) * 0.6, s_y = sin(1.8 t) * 0.4 + 0.8
 EXAMPLE_SCALE = {"c": (0.8, 0.8), "amp": (0.6, 0.4), "omega": (1.5, 1.8), "phase": (-1.0, 0.0)}
+
+
+class AstarParams(C.Structure):
+    """svsdf_astar_params (include/svsdf_c.h)."""
+    _fields_ = [("struct_size", C.c_int), ("start_yaw", C.c_double), ("max_expansions", C.c_longlong), ("slice", C.c_int)]
+
+
+class AstarResult(C.Structure):
+    """svsdf_astar_result (include/svsdf_c.h)."""
+    _fields_ = [("struct_size", C.c_int), ("status", C.c_int), ("path_len", C.c_size_t), ("expansions", C.c_ulonglong),
+                ("pushes", C.c_ulonglong), ("relaxed_open", C.c_ulonglong), ("reopened", C.c_ulonglong),
+                ("launches", C.c_ulonglong), ("stage_counts", C.c_ulonglong * 5), ("g_goal", C.c_double)]
+
+
+ASTAR_STATUS = ["FOUND", "EXHAUSTED", "LIMIT", "OUT_OF_MAP"]     # svsdf_astar_status
 
 
 class OutlineStats(C.Structure):
@@ -198,6 +214,11 @@ def lib():
     L.svsdf_frontend_yaw_free.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_size_t, _ip]
     L.svsdf_kernel_bfs.argtypes = [C.c_ulonglong, C.c_int, C.c_double, _dp, _ip]
     L.svsdf_astar_successors.argtypes = [C.c_void_p, C.c_size_t, _ip, _dp, _u8p, _dp, _u8p]
+    L.svsdf_astar_params_default.argtypes = [C.POINTER(AstarParams)]
+    L.svsdf_astar_params_default.restype = None
+    L.svsdf_astar_search.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(AstarParams), _dp, _ip, C.c_size_t,
+                                     C.POINTER(AstarResult)]
+    L.svsdf_astar_nodes.argtypes = [C.c_void_p, C.POINTER(C.c_byte), _dp, _dp, _dp, _ip, C.c_size_t, _ip]
     L.svsdf_mesh_outline.argtypes = [_dp, C.c_size_t, _ip, C.c_size_t, C.c_double, _dp, C.c_size_t,
                                      C.POINTER(C.c_size_t), _ip]
     L.svsdf_mesh_outline_obj.argtypes = [C.c_char_p, C.c_double, _dp, C.c_size_t, C.POINTER(C.c_size_t), _ip]
@@ -731,6 +752,47 @@ class SvsdfContext:
         self._chk(self.L.svsdf_astar_successors(self.ctx, n, ij.ctypes.data_as(_ip), _p(yaw), ok.ctypes.data_as(u8), _p(cy),
                                                 stage.ctypes.data_as(u8)), "svsdf_astar_successors")
         return ok.astype(bool), cy, stage
+
+    def astar_search(self, start, end, start_yaw=0.0, max_expansions=0, slice=0, capacity=None):
+        """AstarPathSearch(start, end) + getPath (front_end_Astar.hpp:243-390) on the resident map, on the device
+        (svsdf_astar_search).  start / end: world points (x, y, z).  Returns a dict: status ("FOUND", "EXHAUSTED", "LIMIT",
+        "OUT_OF_MAP"), path (n, 3) float64 (centre x, centre y, yaw), cells (n, 2) int32, path_len, and the counters
+        expansions, pushes, relaxed_open, reopened, launches, stage_counts (5,), g_goal.  `capacity` (cells; default: ask
+        first, then fetch) is what the output arrays are sized to."""
+        s, e = _f64(start).reshape(3).copy(), _f64(end).reshape(3).copy()
+        prm = AstarParams()
+        self.L.svsdf_astar_params_default(C.byref(prm))
+        prm.start_yaw, prm.max_expansions, prm.slice = float(start_yaw), int(max_expansions), int(slice)
+        res = AstarResult()
+        res.struct_size = C.sizeof(AstarResult)
+        if capacity is None:     # the search runs once: the first call leaves the path on the device side of the result
+            dims = (C.c_int * 2)()
+            self._chk(self.L.svsdf_astar_nodes(self.ctx, None, None, None, None, None, 0, dims), "svsdf_astar_nodes")
+            capacity = dims[0] * dims[1] + 1
+        n = int(capacity)
+        path = np.zeros((n, 3))
+        cells = np.zeros((n, 2), dtype=np.int32)
+        self._chk(self.L.svsdf_astar_search(self.ctx, _p(s), _p(e), C.byref(prm), _p(path), cells.ctypes.data_as(_ip), n,
+                                            C.byref(res)), "svsdf_astar_search")
+        k = int(res.path_len)
+        out = {"status": ASTAR_STATUS[res.status], "path": path[:k].copy(), "cells": cells[:k].copy(), "path_len": k,
+               "stage_counts": np.array(list(res.stage_counts), dtype=np.uint64), "g_goal": float(res.g_goal)}
+        for key in ("expansions", "pushes", "relaxed_open", "reopened", "launches"):
+            out[key] = int(getattr(res, key))
+        return out
+
+    def astar_nodes(self):
+        """The node records the last astar_search left behind (svsdf_astar_nodes), a dict of (X, Y) arrays: id int8 (0
+        untouched, 1 open, -1 closed), g, f, yaw float64, father_cell int32 (ix * Y + iy; -1 none, -2 the start node)."""
+        dims = (C.c_int * 2)()
+        self._chk(self.L.svsdf_astar_nodes(self.ctx, None, None, None, None, None, 0, dims), "svsdf_astar_nodes")
+        X, Y = dims[0], dims[1]
+        out = {"id": np.zeros((X, Y), dtype=np.int8), "g": np.zeros((X, Y)), "f": np.zeros((X, Y)), "yaw": np.zeros((X, Y)),
+               "father_cell": np.zeros((X, Y), dtype=np.int32)}
+        self._chk(self.L.svsdf_astar_nodes(self.ctx, out["id"].ctypes.data_as(C.POINTER(C.c_byte)), _p(out["g"]), _p(out["f"]),
+                                           _p(out["yaw"]), out["father_cell"].ctypes.data_as(_ip), X * Y, dims),
+                  "svsdf_astar_nodes")
+        return out
 
     def debug_sdf_at(self, coeffs, T, points_xy, t):
         """SDF-at-time of (point, time) pairs on the device with its intermediates (svsdf_debug_sdf_at): (n, 8) array

@@ -336,6 +336,70 @@ int svsdf_kernel_bfs(unsigned long long free_mask, int kernel_count, double fath
 int svsdf_astar_successors(svsdf_ctx *ctx, size_t n, const int *parent_ij, const double *parent_yaw,
                            unsigned char *ok_out, double *child_yaw_out, unsigned char *stage_out);
 
+/* ---- front end: the A* search itself on the resident map (device) -------------------------------- */
+/* Replaces AstarPathSearcher::AstarPathSearch + getPath (front_end_Astar.hpp:243-365, 367-390) and the per-search
+ * AstarPathSearcher::reset (:154-163): the open-set loop runs on the device next to the map svsdf_frontend_set_map left
+ * there, one workgroup per search, and every neighbour goes through the four stages of svsdf_astar_successors.
+ *
+ * Order: the reference's std::multimap<double, GridNode*> pops begin() -- the smallest fScore key and, among equal keys,
+ * the entry inserted first.  The device pops the minimum over (key, insertion sequence number), which is that order.  A
+ * node's key is the fScore it was inserted with: the id == 1 branch (:333-342) lowers gScore / fScore / father of an open
+ * node but leaves its place in the queue, as in the reference.  A node's yaw is the one checkKernelValue handed out when
+ * the node was first discovered (AstarGetSucc :231-234), whatever father it ends up with.  The start node is the
+ * reference's separate startPtr (g = 0, yaw = start_yaw, no father); the map's own start cell only gets id = 1, g = 0,
+ * f = h and never enters the queue.  The goal test is the index comparison at pop time, before expansion: start == goal
+ * gives one cell and 0 expansions.  Edge cost sqrt(i*i + j*j); h = getHeu (:165-182) with dz = 0; no contraction.
+ *
+ * Slices: one launch makes at most `slice` pops and leaves the search state in device memory owned by the context; the
+ * host relaunches until the status is final.  A pop is one removal from the open set: every expansion is one, and so is
+ * the final pop that finds the goal; launches == ceil(pops / slice) with pops = expansions + (status == FOUND).  (An empty
+ * open set and the expansion limit are noticed by the launch that made the last expansion.)  The result does not depend
+ * on `slice`. */
+typedef struct svsdf_astar_params {
+  int struct_size;            /* sizeof(svsdf_astar_params) */
+  double start_yaw;           /* yaw of the start node; the reference hard-codes 0.0 (front_end_Astar.hpp:281) */
+  long long max_expansions;   /* stop with SVSDF_ASTAR_LIMIT after this many expansions; 0: no limit (the reference has none) */
+  int slice;                  /* pops per launch; 0: the library's default (256) */
+} svsdf_astar_params;
+enum svsdf_astar_status {
+  SVSDF_ASTAR_FOUND = 0,      /* the goal was popped (success_flag = true, :302-311) */
+  SVSDF_ASTAR_EXHAUSTED = 1,  /* the open set ran empty (:360-361) */
+  SVSDF_ASTAR_LIMIT = 2,      /* max_expansions expansions were made and the open set is not empty */
+  SVSDF_ASTAR_OUT_OF_MAP = 3  /* isInMap (src/map_manager/src/Gridmap3D.cpp:43-71) fails for start or end (:249-254); no launch */
+};
+typedef struct svsdf_astar_result {
+  int struct_size, status;    /* sizeof(svsdf_astar_result) (set by the caller), enum svsdf_astar_status */
+  size_t path_len;            /* cells of the path, start and goal included; 0 unless FOUND */
+  unsigned long long expansions;    /* calls of AstarGetSucc (:313) */
+  unsigned long long pushes;        /* openSet.insert: the start node's (:283) and the neighbours' (:328, :354) */
+  unsigned long long relaxed_open;  /* id == 1 updates (:335-340) */
+  unsigned long long reopened;      /* id == -1 updates (:347-354); counted among the pushes too */
+  unsigned long long launches;
+  unsigned long long stage_counts[5];   /* successor slots by stage 0..4, as svsdf_astar_successors reports them */
+  double g_goal;              /* gScore of the popped goal; 0 unless FOUND */
+} svsdf_astar_result;
+void svsdf_astar_params_default(svsdf_astar_params *p);
+/* start_xyz / end_xyz: world points as AstarPathSearch(start, end) takes them; their cells by getGridIndex
+ * (Gridmap3D.cpp:137-177).  path_xyyaw (3 doubles per cell: centre x, centre y, yaw -- what getPath returns; the start's
+ * yaw is start_yaw) and path_ij (2 ints per cell) may each be NULL; with both NULL the call only reports path_len.
+ * The search is planar in layer 0 like svsdf_astar_successors: a start or end whose z index is not 0 is
+ * SVSDF_ERR_INVALID (the reference would stay in the start's layer and compare the goal's z index too; its demos have
+ * z = 0).  SVSDF_ERR_INVALID also: no resident map, a wrong struct_size, a start_yaw svsdf_kernel_bfs rejects, slice < 0,
+ * max_expansions < 0, and an output given with capacity_cells < path_len -- then *result is complete all the same and the
+ * search state stays readable (svsdf_astar_nodes), so the call can be repeated with room.  A point outside the map is NOT
+ * an error: SVSDF_OK with status SVSDF_ASTAR_OUT_OF_MAP.  Host-only contexts: SVSDF_ERR_NO_DEVICE.  A multi-device context
+ * uses its first device.  The node records and the open set live in the context (sized at the first search on a map,
+ * released with the map) and are reset at the start of every search (AstarPathSearcher::reset). */
+int svsdf_astar_search(svsdf_ctx *ctx, const double start_xyz[3], const double end_xyz[3],
+                       const svsdf_astar_params *params /* may be NULL */, double *path_xyyaw, int *path_ij,
+                       size_t capacity_cells, svsdf_astar_result *result);
+/* GridNodeMap as the last search left it (GridNode, front_end_Astar.hpp:10-51), [ix * Y + iy]: id (0 untouched, 1 open,
+ * -1 closed), gScore, fScore, yaw, and the father as a cell ix * Y + iy (-1: none, -2: the start node).  Any pointer may be
+ * NULL; with all NULL the call only reports dims2 = {X, Y}.  SVSDF_ERR_INVALID: no map, no search on this map yet,
+ * capacity < X * Y. */
+int svsdf_astar_nodes(const svsdf_ctx *ctx, signed char *id, double *g, double *f, double *yaw, int *father_cell,
+                      size_t capacity, int dims2[2]);
+
 /* ---- mesh shapes (host; BASELINE config 5: "arbitrary .obj mesh, no analytic shape SDF") ------------------------ */
 /* The reference loads conf.inputdata with igl::read_triangle_mesh (src/utils/include/utils/Shape.hpp:281-313) and,
  * when the file's stem is not in its shape registry, plans with the generic Polygon shape over an outline
