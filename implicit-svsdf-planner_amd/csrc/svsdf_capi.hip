@@ -107,13 +107,10 @@ svsdf_ctx *svsdf_create(const svsdf_config *cfg) {
     return nullptr;
   };
   if (hipSetDevice(dev) != hipSuccess) return bail("hipSetDevice failed");
-  {
-    StreamSet ss;   // from the process-wide pool: created once per device, never destroyed (svsdf_ctx.hpp)
-    if (!acquire_streams(dev, ss)) return bail("hipStreamCreate failed");
-    ctx->stream = ss.main;
-    for (int b = 0; b < kMaxBatches; ++b) ctx->bstream[b] = ss.batch[b];
-    ctx->stream_slot = ss.slot;
-  }
+  // from the process-wide pool: created once per device, never destroyed (svsdf_ctx.hpp)
+  if (!acquire_streams(dev, ctx->streams)) return bail("hipStreamCreate failed");
+  ctx->stream = ctx->streams.main;
+  for (int b = 0; b < kMaxBatches; ++b) ctx->bstream[b] = ctx->streams.batch[b];
   // shape constants, evaluated with the host libm exactly where the reference does (SHP:281-294,
   // :855, :1237, :1278, :1320)
   ShapeParams &sp = ctx->sp;
@@ -169,7 +166,7 @@ svsdf_ctx *svsdf_create(const svsdf_config *cfg) {
     const size_t o_slab = align(o_cell + pa.cells.size() * sizeof(PolyRec));
     const size_t o_over = align(o_slab + pa.slabs.size() * sizeof(PolyRec));
     const size_t total = align(o_over + pa.over.size() * sizeof(unsigned short));
-    if (hipMalloc((void **)&ctx->d_poly, total) != hipSuccess) return bail("hipMalloc polygon failed");
+    if (ctx->d_poly.alloc(ctx, total)) return bail("hipMalloc polygon failed");
     std::vector<unsigned char> blob(total, 0);
     pa.hdr.edges = reinterpret_cast<const PolyEdge *>(ctx->d_poly + o_edges);
     pa.hdr.cells = reinterpret_cast<const PolyRec *>(ctx->d_poly + o_cell);
@@ -183,7 +180,7 @@ svsdf_ctx *svsdf_create(const svsdf_config *cfg) {
     if (hipMemcpy(ctx->d_poly, blob.data(), total, hipMemcpyHostToDevice) != hipSuccess)
       return bail("hipMemcpy polygon failed");
     sp.nverts = (int)pa.edges.size();   // entries of the edge array: the vertices + one closing copy per loop of a multi-loop outline
-    sp.accel = reinterpret_cast<const PolyAccel *>(ctx->d_poly);
+    sp.accel = reinterpret_cast<const PolyAccel *>(ctx->d_poly.get());
     sp.edges = pa.hdr.edges;
     // the solve / round kernels keep outlines of up to 1024 edges (48 KB) in LDS in front of the pose table
     ctx->poly_lds = sp.nverts <= kPolyLdsMaxVerts;
@@ -223,13 +220,9 @@ svsdf_ctx *svsdf_create(const svsdf_config *cfg) {
       return bail("event creation failed");
   }
   if (hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming) != hipSuccess) return bail("event creation failed");
-  if (hipMalloc((void **)&ctx->d_traj, sizeof(TrajDev)) != hipSuccess ||
-      hipMalloc((void **)&ctx->d_ctl, kMaxBatches * sizeof(BatchCtl) + 8 * 8 * (kMaxIter + 4)) != hipSuccess ||
-      hipMalloc((void **)&ctx->d_nonfinite, sizeof(int)) != hipSuccess ||
-      hipMalloc((void **)&ctx->d_sums, kOutPartial * sizeof(double)) != hipSuccess ||
-      hipMalloc((void **)&ctx->d_out, kOutDoubles * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void **)&ctx->h_out, kOutDoubles * sizeof(double), hipHostMallocDefault) != hipSuccess ||
-      hipMalloc((void **)&ctx->d_ticket, sizeof(unsigned)) != hipSuccess)
+  if (ctx->d_traj.alloc(ctx, 1) || ctx->d_ctl.alloc_bytes(ctx, kMaxBatches * sizeof(BatchCtl) + 8 * 8 * (kMaxIter + 4)) ||
+      ctx->d_nonfinite.alloc(ctx, 1) || ctx->d_sums.alloc(ctx, kOutPartial) || ctx->d_out.alloc(ctx, kOutDoubles) ||
+      ctx->h_out.alloc(ctx, kOutDoubles) || ctx->d_ticket.alloc(ctx, 1))
     return bail("device allocation failed");
   if (hipMemsetAsync(ctx->d_ticket, 0, sizeof(unsigned), ctx->stream) != hipSuccess) return bail("hipMemset failed");
   {  // the pinned result buffer as the device sees it: k_reduce's last block writes the evaluation's result there directly
@@ -278,38 +271,17 @@ void svsdf_destroy(svsdf_ctx *ctx) {
   if (!ctx->subs.empty() || !ctx->workers.empty()) {
     destroy_group_resources(ctx);
     for (svsdf_ctx *s : ctx->subs) svsdf_destroy(s);
-    delete ctx;
+    delete ctx;   // (the all-reduce buffers free themselves, each on its device)
     return;
   }
   (void)hipSetDevice(ctx->device);
   (void)hipDeviceSynchronize();
-  void *bufs[] = {ctx->d_poly, ctx->d_px, ctx->d_py, ctx->d_traj, ctx->d_in, ctx->d_pose, ctx->d_chunks, ctx->d_ltab,
-                  ctx->d_sdf, ctx->d_t, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy, ctx->gs.pt,
-                  ctx->gs.r, ctx->gs.theta0, ctx->gs.theta_res, ctx->gs.iter, ctx->gs.nsamp, ctx->gs.phase, ctx->gs.req,
-                  ctx->gs.list[0], ctx->gs.list[1], ctx->gs.solve, ctx->gs.sqx, ctx->gs.sqy, ctx->gs.sqth,
-                  ctx->gs.sq_ub, ctx->gs.sq_k, ctx->gs.sq_sdf, ctx->gs.sq_t, ctx->d_ctl,
-                  ctx->d_block_partials, ctx->d_sums,
-                  ctx->d_out, ctx->d_nonfinite, ctx->d_fe, ctx->d_fe_flag, ctx->d_ticket,
-                  ctx->d_fm_occ, ctx->d_fm_free, ctx->d_fm_kt, ctx->d_succ, ctx->d_astar};
-  for (void *p : bufs)
-    if (p) (void)hipFree(p);
-  if (ctx->h_in) (void)hipHostFree(ctx->h_in);
-  if (ctx->h_out) (void)hipHostFree(ctx->h_out);
-  if (ctx->h_fe) (void)hipHostFree(ctx->h_fe);
-  if (ctx->h_succ) (void)hipHostFree(ctx->h_succ);
-  if (ctx->h_astar) (void)hipHostFree(ctx->h_astar);
   for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
   if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);
   for (int b = 0; b < kMaxBatches; ++b)
     if (ctx->ev_done[b]) (void)hipEventDestroy(ctx->ev_done[b]);
-  if (ctx->stream_slot >= 0) {   // the streams go back to the pool (idle: the device was synchronised above)
-    StreamSet ss;
-    ss.main = ctx->stream;
-    for (int b = 0; b < kMaxBatches; ++b) ss.batch[b] = ctx->bstream[b];
-    ss.slot = ctx->stream_slot;
-    release_streams(ctx->device, ss);
-  }
-  delete ctx;
+  if (ctx->streams.slot >= 0) release_streams(ctx->device, ctx->streams);   // back to the pool (idle: the device was synchronised above)
+  delete ctx;   // the buffers go with their owners
 }
 
 int svsdf_set_points(svsdf_ctx *ctx, const double *xyz_aos, size_t P) {
@@ -443,6 +415,11 @@ long long svsdf_debug_sqrt_mismatches(svsdf_ctx *ctx, const double *x, size_t n,
   if (!ctx || ctx->host_only || !x || n == 0 || n > ((size_t)1 << 28) || (flavour != 0 && flavour != 1)) return -1;
   if (!ctx->subs.empty()) return svsdf_debug_sqrt_mismatches(ctx->subs[0], x, n, flavour);
   return sqrt_mismatches(ctx, x, n, flavour);
+}
+
+long long svsdf_debug_live_allocations(long long *bytes) {
+  if (bytes) *bytes = g_live_bytes.load();
+  return g_live_allocs.load();
 }
 
 #ifdef SVSDF_SITE_STATS

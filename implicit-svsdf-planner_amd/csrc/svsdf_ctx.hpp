@@ -3,6 +3,10 @@
 //   svsdf_group.hip     in-process multi-GPU group: worker threads, host / RCCL combine
 //   svsdf_capi.hip      the C ABI of include/svsdf_c.h for the hot path: contexts, points, evaluation, plan, full callback
 //   svsdf_extras.hip    C ABI of the rows around the path: front end, map / mesh helpers, swept outline, L-BFGS driver
+// Memory: every device and pinned allocation of the library is a Buf (below) -- the one place that allocates and frees.
+// A Buf frees in its destructor, on the device it allocated on, so the context, a CloudPlan and a function's scratch
+// release what they hold by going out of scope; no function keeps a list of pointers to free.  Structs that kernels take
+// by value (GsipState, AstarDev, FrontMapDev) stay raw views; their owners sit beside them in the context.
 // Nothing here is part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +14,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -73,16 +78,103 @@ struct Worker {
   }
 };
 
+struct svsdf_ctx;
+
+namespace svsdf_impl {
+
+extern thread_local std::string g_last_error;
+int fail(svsdf_ctx *ctx, int code, const std::string &msg);
+
+// early return of a failed HIP call through fail(); HIPCHK names the call, HIPCHK_AS names what the caller says
+#define HIPCHK_AS(what, expr)                                                                     \
+  do {                                                                                            \
+    hipError_t e_ = (expr);                                                                       \
+    if (e_ != hipSuccess)                                                                         \
+      return fail(ctx, SVSDF_ERR_HIP_BASE + (int)e_, std::string(what) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+#define HIPCHK(expr) HIPCHK_AS(#expr, expr)
+
+// allocations of this library that are live in this process, and their bytes (svsdf_debug_live_allocations)
+inline std::atomic<long long> g_live_allocs{0}, g_live_bytes{0};
+
+// Move-only owner of one device (PINNED: pinned host) allocation.  Reads as a T* at its use sites.
+template <typename T, bool PINNED = false>
+struct Buf {
+  T *p = nullptr;
+  size_t bytes = 0;
+  int dev = 0;   // device that was current at alloc(): the memory is freed there
+  Buf() = default;
+  Buf(Buf &&o) noexcept : p(o.p), bytes(o.bytes), dev(o.dev) { o.p = nullptr; }
+  Buf &operator=(Buf &&o) noexcept {
+    if (this != &o) { reset(); p = o.p; bytes = o.bytes; dev = o.dev; o.p = nullptr; }
+    return *this;
+  }
+  ~Buf() { reset(); }
+  operator T *() const { return p; }
+  T *operator->() const { return p; }
+  T *get() const { return p; }   // (where a template or a reinterpret_cast needs the pointer itself)
+  void reset() {
+    if (!p) return;
+    int cur = dev;
+    (void)hipGetDevice(&cur);
+    if (cur != dev) (void)hipSetDevice(dev);
+    if (PINNED) (void)hipHostFree(p); else (void)hipFree(p);
+    if (cur != dev) (void)hipSetDevice(cur);
+    p = nullptr;
+    --g_live_allocs;
+    g_live_bytes -= (long long)bytes;
+  }
+  // replace with `count` elements (at least one) on the current device; `view`: a raw copy of the new address, for the
+  // structs that kernels take by value
+  int alloc(svsdf_ctx *ctx, size_t count, T **view = nullptr) { return alloc_bytes(ctx, std::max<size_t>(count, 1) * sizeof(T), view); }
+  int alloc_bytes(svsdf_ctx *ctx, size_t n, T **view = nullptr) {   // (for a T with a tail behind it)
+    reset();
+    if (view) *view = nullptr;
+    (void)hipGetDevice(&dev);
+    if (PINNED) HIPCHK(hipHostMalloc((void **)&p, n, hipHostMallocDefault));
+    else HIPCHK_AS("hipMalloc((void **)p, count * sizeof(T))", hipMalloc((void **)&p, n));   // (dev_alloc's text, kept)
+    bytes = n;
+    ++g_live_allocs;
+    g_live_bytes += (long long)bytes;
+    if (view) *view = p;
+    return SVSDF_OK;
+  }
+};
+template <typename T> using PinBuf = Buf<T, true>;
+
+// device buffer + pinned mirror, grown together (cap: elements; reserve below it is free)
+template <typename T>
+struct Staged {
+  Buf<T> d;
+  PinBuf<T> h;
+  size_t cap = 0;
+  int reserve(svsdf_ctx *ctx, size_t n) {
+    if (n <= cap) return SVSDF_OK;
+    cap = 0;
+    int rc = d.alloc(ctx, n);
+    if (rc == SVSDF_OK) rc = h.alloc(ctx, n);
+    if (rc == SVSDF_OK) cap = n;
+    return rc;
+  }
+};
+
+// Streams come from a process-wide pool and go back to it (svsdf_pipeline.hip, acquire_streams)
+struct StreamSet { hipStream_t main = nullptr; hipStream_t batch[svsdf::kMaxBatches] = {}; int slot = -1; };
+
+}  // namespace svsdf_impl
+
 struct svsdf_ctx {
+  template <typename T> using Buf = svsdf_impl::Buf<T>;
+  template <typename T> using PinBuf = svsdf_impl::PinBuf<T>;
   svsdf_config cfg{};
   int device = 0;
+  svsdf_impl::StreamSet streams;              // the set of the process-wide stream pool the two below are copies of
   hipStream_t stream = nullptr;               // main stream: upload, prep, assemble, readback
   hipStream_t bstream[svsdf::kMaxBatches] = {};      // one stream per point batch
-  int stream_slot = -1;                       // which set of the process-wide stream pool these are (acquire_streams)
   hipEvent_t ev_prep = nullptr, ev_done[svsdf::kMaxBatches] = {};
   svsdf::ShapeParams sp{};
   bool poly_lds = false;             // Polygon: k_solve / k_round run their kPolygonLds variants (edges at the start of LDS)
-  unsigned char *d_poly = nullptr;   // Polygon: one device blob [PolyAccel | edges | cell records | slab records | long lists]
+  Buf<unsigned char> d_poly;         // Polygon: one device blob [PolyAccel | edges | cell records | slab records | long lists]
   std::vector<double> poly_xy;       // Polygon: the outline as given (host copy)
   std::vector<int> poly_loops;       // Polygon: vertices per closed loop (empty: one loop)
   std::string err;
@@ -91,21 +183,19 @@ struct svsdf_ctx {
   size_t P = 0;
   bool points_set = false;           // svsdf_set_points was called (P may be 0: an obstacle-free window)
   std::vector<long long> shard_idx;  // original index of shard element j
-  double *d_px = nullptr, *d_py = nullptr;
+  Buf<double> d_px, d_py;
   int nbatch = 1;
   int bstart[svsdf::kMaxBatches] = {}, bcount[svsdf::kMaxBatches] = {};
-  svsdf::BatchCtl *d_ctl = nullptr;
+  Buf<svsdf::BatchCtl> d_ctl;
 
   // trajectory
-  svsdf::TrajDev *d_traj = nullptr;
-  double *d_in = nullptr;  // device staging: coeffs (18N) | T (N) | tk (K)
-  double *h_in = nullptr;  // pinned mirror
-  size_t in_cap = 0;       // doubles
-  svsdf::Pose *d_pose = nullptr;
-  svsdf::Chunk *d_chunks = nullptr;
+  Buf<svsdf::TrajDev> d_traj;
+  svsdf_impl::Staged<double> in;   // staging, device + pinned mirror: coeffs (18N) | T (N) | tk (K) | chunk slack | chunk yaw allowance
+  Buf<svsdf::Pose> d_pose;
+  Buf<svsdf::Chunk> d_chunks;
   size_t pose_cap = 0;
   // pose tables of scan layers 2 and 3 (k_layer_tables): layer 2's K x 21 poses, layer 3's K x 22 x 21 behind them
-  svsdf::Pose *d_ltab = nullptr;
+  Buf<svsdf::Pose> d_ltab;
   size_t ltab_cap = 0;         // seeds (K) the buffer holds; grown on demand, never per evaluation
   int layer_tables = -1;       // plan: -1 by the previous evaluation's solve count, 0 off, 2 layer 2 only, 3 layers 2 and 3 (env SVSDF_LAYER_TABLES; same results)
   int ltab_mode = 0;           // this evaluation: 0 none built, 2 / 3 as above
@@ -177,26 +267,30 @@ struct svsdf_ctx {
   svsdf::ScaleDev scale{};
 
   // per-point / per-sub-query buffers
-  double *d_sdf = nullptr, *d_t = nullptr;
-  double *d_res_sdf = nullptr, *d_res_t = nullptr, *d_res_gx = nullptr, *d_res_gy = nullptr;
-  svsdf::GsipState gs{};
+  Buf<double> d_sdf, d_t;
+  Buf<double> d_res_sdf, d_res_t, d_res_gx, d_res_gy;
+  svsdf::GsipState gs{};          // what the kernels take: raw views of the arrays that gs_own holds
+  struct {
+    Buf<int> pt, iter, nsamp, phase, list[2], solve, sq_k;
+    Buf<unsigned> req;
+    Buf<double> r, theta0, theta_res, sqx, sqy, sqth, sq_ub, sq_sdf, sq_t;
+  } gs_own;
   size_t icap = 0;                // interior capacity: entries of the per-interior-point arrays, stride of the sample arrays
   bool icap_fitted = false;       // capacity already fitted to a measured interior count of this point set
-  double *d_block_partials = nullptr;
+  Buf<double> d_block_partials;
   size_t block_partials_cap = 0;  // doubles
-  double *d_sums = nullptr;       // 19 * kMaxPieces + 1
-  double *d_out = nullptr;        // [partial (19 * kMaxPieces + 1) | 8 x u64 stats]
-  double *h_out = nullptr;        // pinned mirror
+  Buf<double> d_sums;             // 19 * kMaxPieces + 1
+  Buf<double> d_out;              // [partial (19 * kMaxPieces + 1) | 8 x u64 stats]
+  PinBuf<double> h_out;           // pinned mirror
   double *h_out_dev = nullptr;    // the same buffer as the device addresses it (k_reduce writes the result there); null: copy
-  unsigned *d_ticket = nullptr;   // k_reduce: finished-block counter (zero between launches)
-  int *d_nonfinite = nullptr;
+  Buf<unsigned> d_ticket;         // k_reduce: finished-block counter (zero between launches)
+  Buf<int> d_nonfinite;
   int h_nonfinite = 0;
   size_t e_end = 0;
 
-  // front-end batches (row f3): growing device scratch [father | child | pts | kt] + offsets + flags
-  double *d_fe = nullptr, *h_fe = nullptr;   // device buffer + pinned staging mirror
-  size_t fe_cap = 0;                          // doubles
-  int *d_fe_flag = nullptr;
+  // front-end batches (row f3): growing staging [father | child | pts | kt] + offsets (doubles), and the flags
+  svsdf_impl::Staged<double> fe;
+  Buf<int> d_fe_flag;
   std::vector<int> h_fe_flag;
   size_t fe_edges_cap = 0;
 
@@ -204,14 +298,13 @@ struct svsdf_ctx {
   // pinned + device staging of svsdf_astar_successors [parent yaw | parent ij || child yaw | stage]
   bool fm_set = false;
   svsdf::FrontMapDev fm{};
-  unsigned long long *d_fm_occ = nullptr, *d_fm_free = nullptr;
-  double *d_fm_kt = nullptr;
-  unsigned char *d_succ = nullptr, *h_succ = nullptr;
-  size_t succ_cap = 0;                        // parents
+  Buf<unsigned long long> d_fm_occ, d_fm_free;
+  Buf<double> d_fm_kt;
+  svsdf_impl::Staged<unsigned char> succ;     // (97 bytes per parent)
   // svsdf_astar_search: one device blob [state | node records | open set | path], carved up in `astar`; sized for the
   // resident map at the first search on it, released with the map
-  unsigned char *d_astar = nullptr;
-  svsdf::AstarState *h_astar = nullptr;       // pinned: the state goes up once per search and comes back once per launch
+  Buf<unsigned char> d_astar;
+  PinBuf<svsdf::AstarState> h_astar;          // pinned: the state goes up once per search and comes back once per launch
   int fm_Z = 0;                               // layers of the resident map's grid (the search stays in layer 0)
   svsdf::AstarDev astar{};
   bool astar_searched = false;                // the node records hold a search on the resident map
@@ -235,8 +328,8 @@ struct svsdf_ctx {
   std::vector<std::unique_ptr<Worker>> workers;   // one host thread per sub-context
   int combine = 0;                  // SVSDF_COMBINE_HOST / SVSDF_COMBINE_RCCL (resolved)
   std::vector<void *> comms;        // ncclComm_t per sub-context (RCCL combine)
-  std::vector<double *> d_red;      // per sub-context all-reduce output (RCCL combine)
-  double *h_red = nullptr;          // pinned: reduced partial read back from subs[0]
+  std::vector<Buf<double>> d_red;   // per sub-context all-reduce output (RCCL combine)
+  PinBuf<double> h_red;             // pinned: reduced partial read back from subs[0]
   std::vector<double> comb;         // host-combined [cost | gradC | gradT]
   const double *h_partial = nullptr;  // where the last evaluation's summed partial lives on the host
   double combine_ms = 0.0, setup_ms = 0.0, fanout_ms = 0.0;
@@ -263,24 +356,7 @@ constexpr size_t kOutPartial = 19 * svsdf::kMaxPieces + 1;
 constexpr size_t kOutDoubles = kOutPartial + 14 + 2 * svsdf::kMaxIter;   // partial | 9 counters | solves per iteration | round scans | speculative | active per iteration | interior found | clock probe (2)
 constexpr int kRepeat = -12345;   // finish(): more interior points than capacity -- the arrays were grown, repeat the evaluation
 
-extern thread_local std::string g_last_error;
 extern const char *kShapeNames[SVSDF_SHAPE_COUNT];
-int fail(svsdf_ctx *ctx, int code, const std::string &msg);
-
-#define HIPCHK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess)                                                                         \
-      return fail(ctx, SVSDF_ERR_HIP_BASE + (int)e_, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-template <typename T>
-int dev_alloc(svsdf_ctx *ctx, T **p, size_t count) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (count == 0) count = 1;
-  HIPCHK(hipMalloc((void **)p, count * sizeof(T)));
-  return SVSDF_OK;
-}
 
 // Lanes per query of the main solve by shard size: small shards are latency chains (wide groups shorten them), large ones
 // throughput (narrow groups waste fewer lanes; the descent's ladders share the wave anyway).  Crossovers re-measured in
@@ -304,7 +380,6 @@ inline int default_lanes(const svsdf_ctx *ctx, size_t Ps) {
 // get sets 0 and 1; (b) the pool is process-wide static state and its streams are never destroyed, so it must not be
 // relied on across hipDeviceReset(): acquire_streams probes a pooled set with hipStreamQuery and re-creates a dead one,
 // which covers a reset BETWEEN contexts, not one under a live context (that invalidates the context itself).
-struct StreamSet { hipStream_t main = nullptr; hipStream_t batch[svsdf::kMaxBatches] = {}; int slot = -1; };
 bool acquire_streams(int device, StreamSet &out);
 void release_streams(int device, StreamSet &s);
 int set_batches(svsdf_ctx *ctx, int nb);
@@ -329,14 +404,12 @@ int run_pipeline_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double 
 void accumulate(int N, const double *partial, double *cost, double *gradT, double *gradC);
 void shard_plan(const double *xyz, size_t P, int rk, int ws, int flags, std::vector<long long> &out);
 struct CloudPlan {
-  int device = 0;
   const double *d_xyz = nullptr;
   size_t P = 0;
-  double *d_part = nullptr;
-  unsigned long long *d_keys = nullptr, *d_keys2 = nullptr;
+  Buf<double> d_part;
+  Buf<unsigned long long> d_keys, d_keys2;
   const unsigned long long *sorted = nullptr;
-  void *d_tmp = nullptr;
-  void release();
+  Buf<unsigned char> d_tmp;
 };
 int plan_cloud(svsdf_ctx *ctx, const double *d_xyz, size_t P, CloudPlan &plan);
 int take_stripe(svsdf_ctx *ctx, svsdf_ctx *planner, const CloudPlan &plan, int rk, int ws);

@@ -60,32 +60,28 @@ int svsdf_check_sub_sw_collision(svsdf_ctx *ctx, size_t n_edges, const double *f
   HIPCHK(hipSetDevice(ctx->device));
   // one packed upload: [father 3E | child 3E | kt 64 | offsets E+1 (u64) | pts 2T] through a pinned staging buffer
   const size_t need = 6 * n_edges + kMaxKt + (n_edges + 1) + 2 * total;
-  if (need > ctx->fe_cap) {
-    const size_t cap = need + need / 2;
-    int rc = dev_alloc(ctx, &ctx->d_fe, cap);
+  if (need > ctx->fe.cap) {
+    int rc = ctx->fe.reserve(ctx, need + need / 2);
     if (rc) return rc;
-    if (ctx->h_fe) { (void)hipHostFree(ctx->h_fe); ctx->h_fe = nullptr; }
-    HIPCHK(hipHostMalloc((void **)&ctx->h_fe, cap * sizeof(double)));
-    ctx->fe_cap = cap;
   }
   if (n_edges > ctx->fe_edges_cap) {
-    int rc = dev_alloc(ctx, &ctx->d_fe_flag, 2 * n_edges);
+    int rc = ctx->d_fe_flag.alloc(ctx, 2 * n_edges);
     if (rc) return rc;
     ctx->fe_edges_cap = 2 * n_edges;
     ctx->h_fe_flag.resize(2 * n_edges);
   }
-  double *h = ctx->h_fe;
+  double *h = ctx->fe.h;
   std::memcpy(h, father_states, 3 * n_edges * sizeof(double));
   std::memcpy(h + 3 * n_edges, child_states, 3 * n_edges * sizeof(double));
   std::memcpy(h + 6 * n_edges, kt_tab, kMaxKt * sizeof(double));
   unsigned long long *h_offs = reinterpret_cast<unsigned long long *>(h + 6 * n_edges + kMaxKt);
   for (size_t e = 0; e <= n_edges; ++e) h_offs[e] = pts_offset[e];
   std::memcpy(h + 6 * n_edges + kMaxKt + n_edges + 1, pts_xy, 2 * total * sizeof(double));
-  double *d_father = ctx->d_fe, *d_child = d_father + 3 * n_edges, *d_kt = d_child + 3 * n_edges;
+  double *d_father = ctx->fe.d, *d_child = d_father + 3 * n_edges, *d_kt = d_child + 3 * n_edges;
   unsigned long long *d_offs = reinterpret_cast<unsigned long long *>(d_kt + kMaxKt);
   double *d_pts = d_kt + kMaxKt + n_edges + 1;
   hipStream_t st = ctx->stream;
-  HIPCHK(hipMemcpyAsync(ctx->d_fe, h, need * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ctx->fe.d, h, need * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(ctx->d_fe_flag, 0, n_edges * sizeof(int), st));   // hit flags: 1 = some sdf < 0
   const dim3 grid((unsigned)n_edges, (unsigned)((max_pts + kSubswPoints - 1) / kSubswPoints));
   (void)launch_k_subsw(ctx->cfg.shape_id, grid, st, ctx->sp, d_father, d_child, d_offs, d_pts, d_kt, nkt, ctx->d_fe_flag);
@@ -118,25 +114,21 @@ int svsdf_shape_kernels(svsdf_ctx *ctx, int kernel_size, int kernel_count, doubl
   const int size_side = (int)(0.5 * (kernel_size - 1));
   const size_t cells = (size_t)kernel_size * kernel_size;
   HIPCHK(hipSetDevice(ctx->device));
-  double *d_yaw = nullptr;
-  unsigned char *d_map = nullptr;
-  HIPCHK(hipMalloc((void **)&d_yaw, count * sizeof(double)));
-  if (hipMalloc((void **)&d_map, cells * count) != hipSuccess) {
-    (void)hipFree(d_yaw);
-    return fail(ctx, SVSDF_ERR_HIP_BASE + (int)hipErrorOutOfMemory, "svsdf_shape_kernels: hipMalloc");
-  }
+  // (an early return below frees the scratch, and the owner's free waits for the device: nothing queued on the stream still reads
+  // yaws -- declared before d_yaw, so destroyed after it -- or writes map_out once this function has returned)
+  Buf<double> d_yaw;
+  Buf<unsigned char> d_map;
+  int rc = d_yaw.alloc(ctx, count);
+  if (rc == SVSDF_OK) rc = d_map.alloc(ctx, cells * count);
+  if (rc) return rc;
   hipStream_t st = ctx->stream;
-  hipError_t e1 = hipMemcpyAsync(d_yaw, yaws.data(), count * sizeof(double), hipMemcpyHostToDevice, st);
+  HIPCHK_AS("svsdf_shape_kernels", hipMemcpyAsync(d_yaw, yaws.data(), count * sizeof(double), hipMemcpyHostToDevice, st));
   const unsigned grid = (unsigned)((cells * count + kBlock - 1) / kBlock);
   (void)launch_k_shape_kernels(ctx->cfg.shape_id, grid, st, ctx->sp, kernel_size, count, kernel_resolution, size_side,
                                safemargin, d_yaw, d_map);
-  hipError_t e2 = hipGetLastError();
-  hipError_t e3 = hipMemcpyAsync(map_out, d_map, cells * count, hipMemcpyDeviceToHost, st);
-  hipError_t e4 = hipStreamSynchronize(st);
-  (void)hipFree(d_yaw);
-  (void)hipFree(d_map);
-  for (hipError_t e : {e1, e2, e3, e4})
-    if (e != hipSuccess) return fail(ctx, SVSDF_ERR_HIP_BASE + (int)e, std::string("svsdf_shape_kernels: ") + hipGetErrorString(e));
+  HIPCHK_AS("svsdf_shape_kernels", hipGetLastError());
+  HIPCHK_AS("svsdf_shape_kernels", hipMemcpyAsync(map_out, d_map, cells * count, hipMemcpyDeviceToHost, st));
+  HIPCHK_AS("svsdf_shape_kernels", hipStreamSynchronize(st));
   if (yaw_out) std::memcpy(yaw_out, yaws.data(), count * sizeof(double));
   if (bytes_out) {  // byteShapeKernel::generateByteKernel SHP:194-216, or_mask SHP:95
     const int bpl = (kernel_size + 7) / 8;
@@ -199,13 +191,10 @@ int svsdf_pcd_read_ascii(const char *path, float *xyz, size_t capacity, size_t *
 // ---- front end: resident map, yaw-free table, batched successor test ---------------------------------------------
 static void frontend_release(svsdf_ctx *ctx) {
   ctx->fm_set = false;
-  for (void *p : {(void *)ctx->d_fm_occ, (void *)ctx->d_fm_free, (void *)ctx->d_fm_kt})
-    if (p) (void)hipFree(p);
-  ctx->d_fm_occ = ctx->d_fm_free = nullptr;
-  ctx->d_fm_kt = nullptr;
-  // the search state belongs to the map
-  if (ctx->d_astar) (void)hipFree(ctx->d_astar);
-  ctx->d_astar = nullptr;
+  ctx->d_fm_occ.reset();
+  ctx->d_fm_free.reset();
+  ctx->d_fm_kt.reset();
+  ctx->d_astar.reset();   // the search state belongs to the map
   ctx->astar = AstarDev{};
   ctx->astar_searched = false;
 }
@@ -251,41 +240,39 @@ int svsdf_frontend_set_map(svsdf_ctx *ctx, const svsdf_map *map, int kernel_size
   HIPCHK(hipStreamSynchronize(ctx->stream));
   frontend_release(ctx);
   const size_t cells = (size_t)kernel_size * kernel_size;
-  double *d_yaw = nullptr;
-  unsigned char *d_bytes = nullptr;
-  unsigned long long *d_krows = nullptr;
+  Buf<double> d_yaw;
+  Buf<unsigned char> d_bytes;
+  Buf<unsigned long long> d_krows;
   hipStream_t st = ctx->stream;
-  hipError_t err = hipSuccess;
-  bool compiled = true;
-  auto ok = [&](hipError_t e) { if (err == hipSuccess) err = e; return err == hipSuccess; };
-  if (ok(hipMalloc((void **)&d_yaw, kernel_count * sizeof(double))) && ok(hipMalloc((void **)&d_bytes, cells * kernel_count)) &&
-      ok(hipMalloc((void **)&d_krows, (size_t)kernel_size * kernel_count * sizeof(unsigned long long))) &&
-      ok(hipMalloc((void **)&ctx->d_fm_occ, occ.size() * sizeof(unsigned long long))) &&
-      ok(hipMalloc((void **)&ctx->d_fm_free, (size_t)X * Y * sizeof(unsigned long long))) &&
-      ok(hipMalloc((void **)&ctx->d_fm_kt, kMaxKt * sizeof(double))) &&
-      ok(hipMemcpyAsync(d_yaw, yaws.data(), kernel_count * sizeof(double), hipMemcpyHostToDevice, st)) &&
-      ok(hipMemcpyAsync(ctx->d_fm_occ, occ.data(), occ.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st)) &&
-      ok(hipMemcpyAsync(ctx->d_fm_kt, kt_tab, kMaxKt * sizeof(double), hipMemcpyHostToDevice, st))) {
+  const auto build = [&]() -> int {
+    int rc = d_yaw.alloc(ctx, kernel_count);
+    if (rc == SVSDF_OK) rc = d_bytes.alloc(ctx, cells * kernel_count);
+    if (rc == SVSDF_OK) rc = d_krows.alloc(ctx, (size_t)kernel_size * kernel_count);
+    if (rc == SVSDF_OK) rc = ctx->d_fm_occ.alloc(ctx, occ.size());
+    if (rc == SVSDF_OK) rc = ctx->d_fm_free.alloc(ctx, (size_t)X * Y);
+    if (rc == SVSDF_OK) rc = ctx->d_fm_kt.alloc(ctx, kMaxKt);
+    if (rc) return rc;
+    HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(d_yaw, yaws.data(), kernel_count * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(ctx->d_fm_occ, occ.data(), occ.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+    HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(ctx->d_fm_kt, kt_tab, kMaxKt * sizeof(double), hipMemcpyHostToDevice, st));
     // the kernel resolution is the map's: kernelConv overlays kernel cells on map cells one to one
     const unsigned grid = (unsigned)((cells * kernel_count + kBlock - 1) / kBlock);
-    compiled = launch_k_shape_kernels(ctx->cfg.shape_id, grid, st, ctx->sp, kernel_size, kernel_count, m.resolution(), side,
-                                      safemargin, d_yaw, d_bytes);
-    if (compiled && ok(hipGetLastError())) {
-      launch_k_pack_kernel_rows(st, d_bytes, kernel_size, kernel_count, d_krows);
-      if (ok(hipGetLastError())) {
-        launch_k_yaw_free(st, ctx->d_fm_occ, row_words, d_krows, kernel_size, kernel_count, X, Y, ctx->d_fm_free);
-        ok(hipGetLastError());
-      }
-    }
-  }
-  ok(hipStreamSynchronize(st));   // (also before the pageable sources above go out of scope)
-  for (void *p : {(void *)d_yaw, (void *)d_bytes, (void *)d_krows})
-    if (p) (void)hipFree(p);
-  if (err != hipSuccess || !compiled) {
-    frontend_release(ctx);
-    if (!compiled) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: shape not compiled into this library");
-    return fail(ctx, SVSDF_ERR_HIP_BASE + (int)err, std::string("svsdf_frontend_set_map: ") + hipGetErrorString(err));
-  }
+    if (!launch_k_shape_kernels(ctx->cfg.shape_id, grid, st, ctx->sp, kernel_size, kernel_count, m.resolution(), side,
+                                safemargin, d_yaw, d_bytes))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: shape not compiled into this library");
+    HIPCHK_AS("svsdf_frontend_set_map", hipGetLastError());
+    launch_k_pack_kernel_rows(st, d_bytes, kernel_size, kernel_count, d_krows);
+    HIPCHK_AS("svsdf_frontend_set_map", hipGetLastError());
+    launch_k_yaw_free(st, ctx->d_fm_occ, row_words, d_krows, kernel_size, kernel_count, X, Y, ctx->d_fm_free);
+    HIPCHK_AS("svsdf_frontend_set_map", hipGetLastError());
+    return SVSDF_OK;
+  };
+  int rc = build();
+  // on every path: the pageable sources above and the scratch must outlive what the stream still does with them
+  const hipError_t es = hipStreamSynchronize(st);
+  if (rc == SVSDF_OK && es != hipSuccess)
+    rc = fail(ctx, SVSDF_ERR_HIP_BASE + (int)es, std::string("svsdf_frontend_set_map: ") + hipGetErrorString(es));
+  if (rc) { frontend_release(ctx); return rc; }
   FrontMapDev &fm = ctx->fm;
   fm.occ = ctx->d_fm_occ; fm.free_ = ctx->d_fm_free; fm.kt = ctx->d_fm_kt; fm.nkt = nkt;
   fm.X = X; fm.Y = Y; fm.side = side; fm.row_words = row_words; fm.kernel_count = kernel_count;
@@ -348,20 +335,15 @@ int svsdf_astar_successors(svsdf_ctx *ctx, size_t n, const int *parent_ij, const
   constexpr size_t kSuccParents = (size_t)1 << 18;       // parents per launch: 9 blocks each, well inside one grid dimension
   constexpr size_t kIn = 16, kOut = 81;            // bytes per parent: yaw + ij | 9 child yaws + 9 stages
   const size_t want = std::min(n, kSuccParents);
-  if (want > ctx->succ_cap) {
-    const size_t cap = std::min(kSuccParents, want + want / 2);
-    int rc = dev_alloc(ctx, &ctx->d_succ, cap * (kIn + kOut));
+  if (want * (kIn + kOut) > ctx->succ.cap) {
+    int rc = ctx->succ.reserve(ctx, std::min(kSuccParents, want + want / 2) * (kIn + kOut));
     if (rc) return rc;
-    ctx->succ_cap = 0;
-    if (ctx->h_succ) { (void)hipHostFree(ctx->h_succ); ctx->h_succ = nullptr; }
-    HIPCHK(hipHostMalloc((void **)&ctx->h_succ, cap * (kIn + kOut)));
-    ctx->succ_cap = cap;
   }
   hipStream_t st = ctx->stream;
   for (size_t p0 = 0; p0 < n; p0 += kSuccParents) {
     const size_t m = std::min(kSuccParents, n - p0);
     // one upload [yaw m (f64) | ij 2m (i32)], one read-back [child yaw 9m (f64) | stage 9m (u8)]
-    unsigned char *h = ctx->h_succ, *d = ctx->d_succ;
+    unsigned char *h = ctx->succ.h, *d = ctx->succ.d;
     std::memcpy(h, parent_yaw + p0, m * sizeof(double));
     std::memcpy(h + 8 * m, parent_ij + 2 * p0, 2 * m * sizeof(int));
     HIPCHK(hipMemcpyAsync(d, h, kIn * m, hipMemcpyHostToDevice, st));
@@ -396,9 +378,9 @@ static int astar_alloc(svsdf_ctx *ctx) {
   if (cap > 0x7fffffffull) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: map too large");
   const size_t head = 256;
   const size_t bytes = head + 8 * (3 * cells + 3 * cap) + 4 * (cells + 2 * cap) + cells;
-  int rc = dev_alloc(ctx, &ctx->d_astar, bytes);
+  int rc = ctx->d_astar.alloc(ctx, bytes);
+  if (rc == SVSDF_OK && !ctx->h_astar) rc = ctx->h_astar.alloc(ctx, 1);
   if (rc) return rc;
-  if (!ctx->h_astar) HIPCHK(hipHostMalloc((void **)&ctx->h_astar, sizeof(AstarState)));
   static_assert(sizeof(AstarState) <= 256, "state header");
   AstarDev &a = ctx->astar;
   unsigned char *b = ctx->d_astar;

@@ -22,7 +22,6 @@ int upload_group_device(svsdf_ctx *ctx, const double *d_xyz, size_t P) {
     }
   }
   if (rc && ctx->err.empty()) ctx->err = s0->err;
-  plan.release();
   ctx->P = 0;
   ctx->shard_idx.clear();
   for (svsdf_ctx *s : ctx->subs) {
@@ -186,7 +185,7 @@ int run_pipeline_group(svsdf_ctx *ctx, int N, const double *coeffs, const double
   const auto t0 = std::chrono::steady_clock::now();
   ctx->comb.resize(kOutPartial);
   if (rccl) {
-    std::copy(ctx->h_red, ctx->h_red + plen, ctx->comb.begin());
+    std::copy(ctx->h_red.get(), ctx->h_red + plen, ctx->comb.begin());
   } else {
     // fixed-order host sum of G pinned partials (G x 5 KB): deterministic, no extra launch or sync
     for (size_t e = 0; e < plen; ++e) {
@@ -214,15 +213,18 @@ int set_points_host(svsdf_ctx *ctx, const double *xyz, size_t P) {
   const auto t0 = std::chrono::steady_clock::now();
   svsdf_ctx *s0 = ctx->subs.empty() ? ctx : ctx->subs[0];
   HIPCHK(hipSetDevice(s0->device));
-  double *d_xyz = nullptr;
+  Buf<double> d_xyz;   // on s0's device
   if (P) {
-    HIPCHK(hipMalloc((void **)&d_xyz, 3 * P * sizeof(double)));
+    int rc = d_xyz.alloc(ctx, 3 * P);
+    if (rc) return rc;
     const hipError_t e = hipMemcpy(d_xyz, xyz, 3 * P * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d_xyz); return fail(ctx, SVSDF_ERR_HIP_BASE + (int)e, "upload of the query points failed"); }
+    if (e != hipSuccess) return fail(ctx, SVSDF_ERR_HIP_BASE + (int)e, "upload of the query points failed");
   }
   const int rc = ctx->subs.empty() ? upload_shard_device(ctx, d_xyz, P, ctx->cfg.rank, ctx->cfg.world_size)
                                    : upload_group_device(ctx, d_xyz, P);
-  if (d_xyz) { (void)hipSetDevice(s0->device); (void)hipFree(d_xyz); }
+  // as before this owner existed: after staging a cloud the calling thread ends on the cloud's device (an empty cloud stages
+  // nothing and leaves the thread where the stripes left it); d_xyz is then freed without a device switch
+  if (d_xyz) (void)hipSetDevice(s0->device);
   ctx->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   for (svsdf_ctx *s : ctx->subs) s->setup_ms = ctx->setup_ms;
   return rc;
@@ -254,17 +256,14 @@ std::string group_init_rccl(svsdf_ctx *g) {
     for (int k = 0; k < G; ++k)
       if (g->comms[k] && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(g->comms[k]);
     g->comms.clear();
-    for (size_t k = 0; k < g->d_red.size(); ++k)
-      if (g->d_red[k]) { (void)hipSetDevice(devs[k]); (void)hipFree(g->d_red[k]); }
     g->d_red.clear();
     return m;
   };
-  g->d_red.assign(G, nullptr);
+  g->d_red.resize(G);
   for (int k = 0; k < G; ++k)
-    if (hipSetDevice(devs[k]) != hipSuccess || hipMalloc((void **)&g->d_red[k], kOutPartial * sizeof(double)) != hipSuccess)
+    if (hipSetDevice(devs[k]) != hipSuccess || g->d_red[k].alloc(g, kOutPartial))
       return undo("allocation of the all-reduce buffer failed");
-  if (!g->h_red && hipHostMalloc((void **)&g->h_red, kOutPartial * sizeof(double), hipHostMallocDefault) != hipSuccess)
-    return undo("pinned allocation failed");
+  if (!g->h_red && g->h_red.alloc(g, kOutPartial)) return undo("pinned allocation failed");
   return "";
 }
 
@@ -308,14 +307,12 @@ svsdf_ctx *create_group(const svsdf_config *cfg, int ndev) {
   return g;
 }
 
-// svsdf_destroy of a group: threads, communicators, all-reduce buffers (the sub-contexts are destroyed by the caller)
+// svsdf_destroy of a group: threads, communicators (the sub-contexts are destroyed by the caller, the all-reduce
+// buffers by their owners)
 void destroy_group_resources(svsdf_ctx *ctx) {
   ctx->workers.clear();   // joins the threads
   for (size_t k = 0; k < ctx->comms.size(); ++k)
     if (ctx->comms[k] && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(ctx->comms[k]);
-  for (size_t k = 0; k < ctx->d_red.size(); ++k)
-    if (ctx->d_red[k]) { (void)hipSetDevice(ctx->subs[k]->device); (void)hipFree(ctx->d_red[k]); }
-  if (ctx->h_red) (void)hipHostFree(ctx->h_red);
 }
 
 // rank count of the group's communicator as RCCL reports it (0: none)

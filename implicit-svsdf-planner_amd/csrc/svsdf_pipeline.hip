@@ -191,7 +191,7 @@ size_t table_lds_doubles(const svsdf_ctx *ctx) {
 void launch_solve(svsdf_ctx *ctx, int G, hipStream_t st, const QuerySet &qs, long long max_queries, double *out_sdf,
                   double *out_t, BatchCtl *ctl, int work_idx,
                   double cull_thresh = std::numeric_limits<double>::infinity()) {
-  const double *d_tk = ctx->d_in + 19 * (size_t)ctx->N;
+  const double *d_tk = ctx->in.d + 19 * (size_t)ctx->N;
   if (ctx->scaled) {
     // the scaled path (§4c): its widths only, and no cull -- both culls bound the rigid map, not the scaled descent's value
     G = scaled_lanes(G);
@@ -334,7 +334,7 @@ void launch_tail(svsdf_ctx *ctx, hipStream_t st, int b, int it0) {
   const int ppw = (pts <= (long long)ctx->n_cu * 12) ? 1 : 2;
   const long long per_block = (kTailBlock / 64) * ppw;
   const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((pts + per_block - 1) / per_block, (long long)ctx->n_cu * 3));
-  const double *d_tk = ctx->d_in + 19 * (size_t)ctx->N;
+  const double *d_tk = ctx->in.d + 19 * (size_t)ctx->N;
   const TailLaunch a{ctx->d_traj, d_tk, ctx->d_pose, ctx->d_chunks, ctx->sp, ctx->d_px, ctx->d_py, ctx->gs, ctx->icap, it0, mode,
                      sel, ctx->select_delta, all_after, ppw, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
                      ctx->d_ctl + b, ctx->round_list | (local ? 4 : 0) | (ctx->tail_duo ? 0 : 8) | ((ctx->scan_anchors && ctx->lipschitz_ok) ? 16 : 0), ctx->prune,
@@ -411,31 +411,26 @@ int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bo
   for (double t = 0.0; t <= dur; t += 0.15) ++K;
   if (K < 1 || K > 16000) return fail(ctx, SVSDF_ERR_INVALID, "trajectory duration out of range for the scan table");
   const size_t need = 19 * (size_t)N + K + 2 * ((K + kChunk - 1) / kChunk);  // coeffs | T | tk | chunk slack | chunk yaw allowance
-  if (need > ctx->in_cap) {
-    const size_t cap = need + 4096;
-    if (ctx->h_in) (void)hipHostFree(ctx->h_in);
-    ctx->h_in = nullptr;
-    HIPCHK(hipHostMalloc((void **)&ctx->h_in, cap * sizeof(double), hipHostMallocDefault));
-    int rc = dev_alloc(ctx, &ctx->d_in, cap);
+  if (need > ctx->in.cap) {
+    int rc = ctx->in.reserve(ctx, need + 4096);
     if (rc) return rc;
-    ctx->in_cap = cap;
   }
   if (K > ctx->pose_cap) {
-    int rc = dev_alloc(ctx, &ctx->d_pose, K + 1024);
+    int rc = ctx->d_pose.alloc(ctx, K + 1024);
     if (rc) return rc;
-    rc = dev_alloc(ctx, &ctx->d_chunks, 2 * ((K + 1024) / kChunk + 2));   // chunk records, then the anchor table (ChunkAnchor, k_prep)
+    rc = ctx->d_chunks.alloc(ctx, 2 * ((K + 1024) / kChunk + 2));   // chunk records, then the anchor table (ChunkAnchor, k_prep)
     if (rc) return rc;
     ctx->pose_cap = K + 1024;
   }
-  std::memcpy(ctx->h_in, coeffs, sizeof(double) * 18 * N);
-  std::memcpy(ctx->h_in + 18 * N, T, sizeof(double) * N);
+  std::memcpy(ctx->in.h, coeffs, sizeof(double) * 18 * N);
+  std::memcpy(ctx->in.h + 18 * N, T, sizeof(double) * N);
   {
-    double *tk = ctx->h_in + 19 * N;
+    double *tk = ctx->in.h + 19 * N;
     size_t k = 0;
     for (double t = 0.0; t <= dur; t += 0.15) tk[k++] = t;
   }
   for (size_t i = 0; i < 19 * (size_t)N; ++i)
-    if (!std::isfinite(ctx->h_in[i])) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite trajectory input");
+    if (!std::isfinite(ctx->in.h[i])) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite trajectory input");
   {
     // Exact cull (k_solve, main points): a point is skipped when  min_c(|p - c_c| - rb_c - slack_c) > safety_hor.
     // Chunk c holds the table times t_k0 .. t_k1; every t of [t_k0 - h, t_k1 + h] lies within h of one of them
@@ -445,10 +440,10 @@ int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bo
     // |p - c_c| - rb_c - V_c * h for every continuous t, whatever local minimum the reference's search returns,
     // and smoothedL1 (BEO:316-340) is inactive.  Only in the regular regime (traj_duration not stale).
     const size_t nch = (K + kChunk - 1) / kChunk;
-    double *slack = ctx->h_in + 19 * (size_t)N + K;
+    double *slack = ctx->in.h + 19 * (size_t)N + K;
     double *rot = slack + nch;   // W_c * h: yaw-rate allowance of the value-based second cull (scan_layer1)
     ctx->slack_max = 0.0;
-    const double *tk = ctx->h_in + 19 * (size_t)N;
+    const double *tk = ctx->in.h + 19 * (size_t)N;
     ctx->cull_ok = (td == dur) && K >= 1;
     std::vector<double> S(N + 1, 0.0);
     for (int i = 0; i < N; ++i) S[i + 1] = S[i] + T[i];
@@ -509,11 +504,11 @@ int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bo
   }
   ctx->N = N;
   ctx->K = (int)K;
-  HIPCHK(hipMemcpyAsync(ctx->d_in, ctx->h_in, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->in.d, ctx->in.h, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   const size_t lds = (size_t)traj_lds_doubles(N) * sizeof(double);
   // one block of 1024 threads (round 6; 256 before): a pose per thread for the ~ 600 poses of a reference-scale trajectory
   // instead of three one after the other, and four waves per SIMD to hide the chain's latencies behind
-  hipLaunchKernelGGL(k_prep, dim3(1), dim3(1024), lds, ctx->stream, ctx->d_in, N, dur, (int)K,
+  hipLaunchKernelGGL(k_prep, dim3(1), dim3(1024), lds, ctx->stream, ctx->in.d, N, dur, (int)K,
                      ctx->piece_time_mode, ctx->d_traj,
                      ctx->d_pose, ctx->d_chunks, ctx->r_bound, ctx->d_ctl, ctx->nbatch, clear_nonfinite ? ctx->d_nonfinite : nullptr);
   (void)record_launch(ctx, SVSDF_KERNEL_PREP, -1, 1, 1024, lds, (long long)K, 0);
@@ -539,14 +534,14 @@ int build_layer_tables(svsdf_ctx *ctx) {
   if (K > ctx->ltab_cap) {
     const size_t cap = K + 256;
     ctx->ltab_cap = 0;
-    int rc = dev_alloc(ctx, &ctx->d_ltab, cap * (size_t)svsdf::kLayerRows * svsdf::kLayerSteps);
+    int rc = ctx->d_ltab.alloc(ctx, cap * (size_t)svsdf::kLayerRows * svsdf::kLayerSteps);
     if (rc) return rc;
     ctx->ltab_cap = cap;
   }
   const int rows = (mode >= 3) ? svsdf::kLayerRows : 1;
   const size_t lds = (size_t)traj_lds_doubles(ctx->N) * sizeof(double);
   const unsigned grid = (unsigned)((K * (size_t)rows * svsdf::kLayerSteps + 255) / 256);
-  hipLaunchKernelGGL(k_layer_tables, dim3(grid), dim3(256), lds, ctx->stream, ctx->d_traj, ctx->d_in + 19 * (size_t)ctx->N, (int)K, rows, ctx->d_ltab);
+  hipLaunchKernelGGL(k_layer_tables, dim3(grid), dim3(256), lds, ctx->stream, ctx->d_traj, ctx->in.d + 19 * (size_t)ctx->N, (int)K, rows, ctx->d_ltab);
   if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_LAYER_TABLES, -1, grid, 256, lds, (long long)(K * rows * svsdf::kLayerSteps), 0)) r->targ[0] = mode;
   ctx->ltab_mode = mode;
   return SVSDF_OK;
@@ -691,7 +686,7 @@ int reduce_and_read(svsdf_ctx *ctx, bool with_partial) {
     const unsigned grid = (unsigned)std::min<size_t>((ctx->P + kBlock - 1) / kBlock, 512);   // (256 / 1024 / 2048 blocks: within 1 %, round 6)
     const size_t plen = 19 * (size_t)N + 1;
     if ((size_t)grid * plen > ctx->block_partials_cap) {
-      int rc = dev_alloc(ctx, &ctx->d_block_partials, (size_t)grid * plen);
+      int rc = ctx->d_block_partials.alloc(ctx, (size_t)grid * plen);
       if (rc) return rc;
       ctx->block_partials_cap = (size_t)grid * plen;
     }
@@ -1022,41 +1017,41 @@ int alloc_interior_buffers(svsdf_ctx *ctx, size_t cap) {
   int rc = 0;
   cap = std::max<size_t>(cap, 1);
   if (cap * kMaxSlots > 0x7fffffffull) return fail(ctx, SVSDF_ERR_INVALID, "too many interior points per shard (max ~89M)");
-  if ((rc = dev_alloc(ctx, &ctx->gs.pt, cap))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.r, cap))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.theta0, cap))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.theta_res, cap))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.iter, cap))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.nsamp, cap))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.phase, cap))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.req, cap))) return rc;
+  if ((rc = ctx->gs_own.pt.alloc(ctx, cap, &ctx->gs.pt))) return rc;
+  if ((rc = ctx->gs_own.r.alloc(ctx, cap, &ctx->gs.r))) return rc;
+  if ((rc = ctx->gs_own.theta0.alloc(ctx, cap, &ctx->gs.theta0))) return rc;
+  if ((rc = ctx->gs_own.theta_res.alloc(ctx, cap, &ctx->gs.theta_res))) return rc;
+  if ((rc = ctx->gs_own.iter.alloc(ctx, cap, &ctx->gs.iter))) return rc;
+  if ((rc = ctx->gs_own.nsamp.alloc(ctx, cap, &ctx->gs.nsamp))) return rc;
+  if ((rc = ctx->gs_own.phase.alloc(ctx, cap, &ctx->gs.phase))) return rc;
+  if ((rc = ctx->gs_own.req.alloc(ctx, cap, &ctx->gs.req))) return rc;
   const size_t S = cap * kMaxSlots;
-  if ((rc = dev_alloc(ctx, &ctx->gs.sqx, S))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.sqy, S))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.sqth, S))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.sq_ub, S))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.sq_k, S))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.sq_sdf, S))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.sq_t, S))) return rc;
+  if ((rc = ctx->gs_own.sqx.alloc(ctx, S, &ctx->gs.sqx))) return rc;
+  if ((rc = ctx->gs_own.sqy.alloc(ctx, S, &ctx->gs.sqy))) return rc;
+  if ((rc = ctx->gs_own.sqth.alloc(ctx, S, &ctx->gs.sqth))) return rc;
+  if ((rc = ctx->gs_own.sq_ub.alloc(ctx, S, &ctx->gs.sq_ub))) return rc;
+  if ((rc = ctx->gs_own.sq_k.alloc(ctx, S, &ctx->gs.sq_k))) return rc;
+  if ((rc = ctx->gs_own.sq_sdf.alloc(ctx, S, &ctx->gs.sq_sdf))) return rc;
+  if ((rc = ctx->gs_own.sq_t.alloc(ctx, S, &ctx->gs.sq_t))) return rc;
   ctx->icap = cap;
   return SVSDF_OK;
 }
 
 int alloc_point_buffers(svsdf_ctx *ctx, size_t P) {
   int rc = 0;
-  if ((rc = dev_alloc(ctx, &ctx->d_px, P))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->d_py, P))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->d_sdf, P))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->d_t, P))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->d_res_sdf, P))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->d_res_t, P))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->d_res_gx, P))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->d_res_gy, P))) return rc;
+  if ((rc = ctx->d_px.alloc(ctx, P))) return rc;
+  if ((rc = ctx->d_py.alloc(ctx, P))) return rc;
+  if ((rc = ctx->d_sdf.alloc(ctx, P))) return rc;
+  if ((rc = ctx->d_t.alloc(ctx, P))) return rc;
+  if ((rc = ctx->d_res_sdf.alloc(ctx, P))) return rc;
+  if ((rc = ctx->d_res_t.alloc(ctx, P))) return rc;
+  if ((rc = ctx->d_res_gx.alloc(ctx, P))) return rc;
+  if ((rc = ctx->d_res_gy.alloc(ctx, P))) return rc;
   // per batch, in the batch's range of the point arrays: the two active lists (compact interior indices) and the
   // solve list (up to kMaxSlots requests per point of the batch)
-  if ((rc = dev_alloc(ctx, &ctx->gs.list[0], P))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.list[1], P))) return rc;
-  if ((rc = dev_alloc(ctx, &ctx->gs.solve, P * kMaxSlots))) return rc;
+  if ((rc = ctx->gs_own.list[0].alloc(ctx, P, &ctx->gs.list[0]))) return rc;
+  if ((rc = ctx->gs_own.list[1].alloc(ctx, P, &ctx->gs.list[1]))) return rc;
+  if ((rc = ctx->gs_own.solve.alloc(ctx, P * kMaxSlots, &ctx->gs.solve))) return rc;
   // the interior-sized arrays start at half the cloud (a corridor cloud has 25 - 40 % interior points) and are fitted
   // to the measured count after the first evaluation; an evaluation that needs more grows them and runs again
   ctx->icap_fitted = false;
@@ -1152,38 +1147,26 @@ int set_batches(svsdf_ctx *ctx, int nb) {
 // (svsdf_shard_plan), so both give the same order (tests/test_points_upload_gpu.py).  1 M points: ~2 ms on the device
 // (+ ~4 ms PCIe when the cloud comes from host memory) against 29 ms for round 1's host radix sort.
 // The plan is made ONCE per cloud; every context of a multi-device group then takes its stripe from it (take_stripe).
-void CloudPlan::release() {
-  (void)hipSetDevice(device);
-  for (void *q : {(void *)d_part, (void *)d_keys, (void *)d_keys2, d_tmp})
-    if (q) (void)hipFree(q);
-  d_part = nullptr; d_keys = d_keys2 = nullptr; d_tmp = nullptr; sorted = nullptr;
-}
-
 int plan_cloud(svsdf_ctx *ctx, const double *d_xyz, size_t P, CloudPlan &plan) {
-  plan.device = ctx->device;
   plan.d_xyz = d_xyz;
   plan.P = P;
   if (P > 0x7fffffffull) return fail(ctx, SVSDF_ERR_INVALID, "too many points (max 2^31 - 1 per call)");
   if (P == 0) return SVSDF_OK;
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-#define UPCHK(expr)                                                                                                  \
-  do {                                                                                                               \
-    hipError_t e_ = (expr);                                                                                          \
-    if (e_ != hipSuccess) { plan.release(); return fail(ctx, SVSDF_ERR_HIP_BASE + (int)e_, std::string(#expr) + ": " + hipGetErrorString(e_)); } \
-  } while (0)
   const unsigned grid = (unsigned)std::min<size_t>((P + kBlock - 1) / kBlock, 1024);
-  UPCHK(hipMalloc((void **)&plan.d_part, (size_t)grid * 4 * sizeof(double)));
-  UPCHK(hipMalloc((void **)&plan.d_keys, P * sizeof(unsigned long long)));
-  UPCHK(hipMalloc((void **)&plan.d_keys2, P * sizeof(unsigned long long)));
-  UPCHK(hipMemsetAsync(ctx->d_nonfinite, 0, sizeof(int), st));
+  int rc = plan.d_part.alloc(ctx, (size_t)grid * 4);
+  if (rc == SVSDF_OK) rc = plan.d_keys.alloc(ctx, P);
+  if (rc == SVSDF_OK) rc = plan.d_keys2.alloc(ctx, P);
+  if (rc) return rc;
+  HIPCHK(hipMemsetAsync(ctx->d_nonfinite, 0, sizeof(int), st));
   hipLaunchKernelGGL(k_points_bbox, dim3(grid), dim3(kBlock), 0, st, d_xyz, P, plan.d_part, ctx->d_nonfinite);
   std::vector<double> hp((size_t)grid * 4);
   int bad = 0;
-  UPCHK(hipMemcpyAsync(hp.data(), plan.d_part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-  UPCHK(hipMemcpyAsync(&bad, ctx->d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
-  UPCHK(hipStreamSynchronize(st));
-  if (bad) { plan.release(); return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite query point"); }
+  HIPCHK(hipMemcpyAsync(hp.data(), plan.d_part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(&bad, ctx->d_nonfinite, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (bad) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite query point");
   double xmin = hp[0], xmax = hp[1], ymin = hp[2], ymax = hp[3];
   for (unsigned b = 1; b < grid; ++b) {
     xmin = std::min(xmin, hp[4 * b]); xmax = std::max(xmax, hp[4 * b + 1]);
@@ -1195,14 +1178,13 @@ int plan_cloud(svsdf_ctx *ctx, const double *d_xyz, size_t P, CloudPlan &plan) {
   plan.sorted = plan.d_keys;
   if (!keep) {
     size_t tmp_bytes = 0;
-    UPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, plan.d_keys, plan.d_keys2, (int)P, 0, 64, st));
-    UPCHK(hipMalloc(&plan.d_tmp, std::max<size_t>(tmp_bytes, 16)));
-    UPCHK(hipcub::DeviceRadixSort::SortKeys(plan.d_tmp, tmp_bytes, plan.d_keys, plan.d_keys2, (int)P, 0, 64, st));
+    HIPCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, plan.d_keys.get(), plan.d_keys2.get(), (int)P, 0, 64, st));
+    if ((rc = plan.d_tmp.alloc(ctx, std::max<size_t>(tmp_bytes, 16)))) return rc;
+    HIPCHK(hipcub::DeviceRadixSort::SortKeys(plan.d_tmp.get(), tmp_bytes, plan.d_keys.get(), plan.d_keys2.get(), (int)P, 0, 64, st));
     plan.sorted = plan.d_keys2;
   }
-  UPCHK(hipStreamSynchronize(st));
-  UPCHK(hipGetLastError());
-#undef UPCHK
+  HIPCHK(hipStreamSynchronize(st));
+  HIPCHK(hipGetLastError());
   return SVSDF_OK;
 }
 
@@ -1228,35 +1210,22 @@ int take_stripe(svsdf_ctx *ctx, svsdf_ctx *planner, const CloudPlan &plan, int r
     const bool local = planner == ctx;
     HIPCHK(hipSetDevice(planner->device));
     hipStream_t st = planner->stream;
-    long long *d_idx = nullptr;
-    double *d_sx = nullptr, *d_sy = nullptr;
-    auto cleanup = [&]() {
-      (void)hipSetDevice(planner->device);
-      for (void *q : {(void *)d_idx, (void *)d_sx, (void *)d_sy})
-        if (q) (void)hipFree(q);
-    };
-#define UPCHK(expr)                                                                                                  \
-  do {                                                                                                               \
-    hipError_t e_ = (expr);                                                                                          \
-    if (e_ != hipSuccess) { cleanup(); return fail(ctx, SVSDF_ERR_HIP_BASE + (int)e_, std::string(#expr) + ": " + hipGetErrorString(e_)); } \
-  } while (0)
-    UPCHK(hipMalloc((void **)&d_idx, Ps * sizeof(long long)));
-    if (!local) {
-      UPCHK(hipMalloc((void **)&d_sx, Ps * sizeof(double)));
-      UPCHK(hipMalloc((void **)&d_sy, Ps * sizeof(double)));
-    }
+    Buf<long long> d_idx;   // staging on the planner's device, freed there
+    Buf<double> d_sx, d_sy;
+    rc = d_idx.alloc(ctx, Ps);
+    if (rc == SVSDF_OK && !local) rc = d_sx.alloc(ctx, Ps);
+    if (rc == SVSDF_OK && !local) rc = d_sy.alloc(ctx, Ps);
+    if (rc) return rc;
     const unsigned g2 = (unsigned)std::min<size_t>((Ps + kBlock - 1) / kBlock, 1024);
     hipLaunchKernelGGL(k_points_gather, dim3(g2), dim3(kBlock), 0, st, plan.d_xyz, plan.sorted, P, rk, ws, Ps,
-                       local ? ctx->d_px : d_sx, local ? ctx->d_py : d_sy, d_idx);
-    UPCHK(hipMemcpyAsync(ctx->shard_idx.data(), d_idx, Ps * sizeof(long long), hipMemcpyDeviceToHost, st));
-    UPCHK(hipStreamSynchronize(st));
-    UPCHK(hipGetLastError());
+                       local ? ctx->d_px.get() : d_sx.get(), local ? ctx->d_py.get() : d_sy.get(), d_idx.get());
+    HIPCHK(hipMemcpyAsync(ctx->shard_idx.data(), d_idx, Ps * sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipGetLastError());
     if (!local) {
-      UPCHK(hipMemcpyPeer(ctx->d_px, ctx->device, d_sx, planner->device, Ps * sizeof(double)));
-      UPCHK(hipMemcpyPeer(ctx->d_py, ctx->device, d_sy, planner->device, Ps * sizeof(double)));
+      HIPCHK(hipMemcpyPeer(ctx->d_px, ctx->device, d_sx, planner->device, Ps * sizeof(double)));
+      HIPCHK(hipMemcpyPeer(ctx->d_py, ctx->device, d_sy, planner->device, Ps * sizeof(double)));
     }
-#undef UPCHK
-    cleanup();
   }
   HIPCHK(hipSetDevice(ctx->device));
   ctx->P = Ps;
@@ -1292,9 +1261,7 @@ int upload_shard_device(svsdf_ctx *ctx, const double *d_xyz, size_t P, int rk, i
   CloudPlan plan;
   int rc = plan_cloud(ctx, d_xyz, P, plan);
   if (rc) { ctx->P = 0; ctx->points_set = false; return rc; }
-  rc = take_stripe(ctx, ctx, plan, rk, ws);
-  plan.release();
-  return rc;
+  return take_stripe(ctx, ctx, plan, rk, ws);
 }
 
 // svsdf_debug_sdf_at: upload the trajectory (same path as an evaluation: k_prep, piece-time mode), evaluate on the device
@@ -1308,33 +1275,29 @@ int debug_sdf_at(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, s
   (void)hipEventRecord(ctx->ev_pool[e0], ctx->stream);
   int rc = upload_traj(ctx, N, coeffs, T);
   if (rc) return rc;
-  double *d_p = nullptr, *d_t = nullptr, *d_o = nullptr;
-  auto cleanup = [&]() { for (void *q : {(void *)d_p, (void *)d_t, (void *)d_o}) if (q) (void)hipFree(q); };
-  hipError_t e = hipMalloc((void **)&d_p, 2 * n * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void **)&d_t, n * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void **)&d_o, 8 * n * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpyAsync(d_p, pxy, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_t, t, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) {
-    const size_t lds = (size_t)traj_lds_doubles(N) * sizeof(double);
-    if (!launch_k_debug_sdf_at(ctx->cfg.shape_id, (unsigned)((n + 63) / 64), lds, ctx->stream, ctx->d_traj, ctx->sp, d_p, d_t, (int)n, d_o,
-                               ctx->scaled ? &ctx->scale : nullptr)) {
-      cleanup();
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_debug_sdf_at: shape not compiled into this build");
-    }
-    e = hipGetLastError();   // a failed launch is this function's error, not the next evaluation's
-    if (e == hipSuccess) e = hipMemcpyAsync(out8, d_o, 8 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  cleanup();
-  if (e != hipSuccess) return fail(ctx, SVSDF_ERR_HIP_BASE + (int)e, std::string("svsdf_debug_sdf_at: ") + hipGetErrorString(e));
+  // (an early return below frees the scratch, and the owner's free waits for the device: no queued copy still reads pxy / t or
+  // writes out8 once this function has returned)
+  Buf<double> d_p, d_t, d_o;
+  rc = d_p.alloc(ctx, 2 * n);
+  if (rc == SVSDF_OK) rc = d_t.alloc(ctx, n);
+  if (rc == SVSDF_OK) rc = d_o.alloc(ctx, 8 * n);
+  if (rc) return rc;
+  HIPCHK_AS("svsdf_debug_sdf_at", hipMemcpyAsync(d_p, pxy, 2 * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK_AS("svsdf_debug_sdf_at", hipMemcpyAsync(d_t, t, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const size_t lds = (size_t)traj_lds_doubles(N) * sizeof(double);
+  if (!launch_k_debug_sdf_at(ctx->cfg.shape_id, (unsigned)((n + 63) / 64), lds, ctx->stream, ctx->d_traj, ctx->sp, d_p, d_t, (int)n, d_o,
+                             ctx->scaled ? &ctx->scale : nullptr))
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_debug_sdf_at: shape not compiled into this build");
+  HIPCHK_AS("svsdf_debug_sdf_at", hipGetLastError());   // a failed launch is this function's error, not the next evaluation's
+  HIPCHK_AS("svsdf_debug_sdf_at", hipMemcpyAsync(out8, d_o, 8 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK_AS("svsdf_debug_sdf_at", hipStreamSynchronize(ctx->stream));
   return SVSDF_OK;
 }
 
 // mismatch count of the kernels' inlined sincos against the device library's (svsdf_debug_sincos_mismatches)
 long long sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, int n) {
   if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-  unsigned long long *d = reinterpret_cast<unsigned long long *>(ctx->d_out);
+  unsigned long long *d = reinterpret_cast<unsigned long long *>(ctx->d_out.get());
   if (hipMemsetAsync(d, 0, sizeof(unsigned long long), ctx->stream) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_sincos_check, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, lo, hi, n, d);
   unsigned long long h = 0;
@@ -1347,19 +1310,18 @@ long long sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, int n) {
 // mismatch count of the kernels' unscaled sqrt against sqrt on n host operands (svsdf_debug_sqrt_mismatches)
 long long sqrt_mismatches(svsdf_ctx *ctx, const double *x, size_t n, int flavour) {
   if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-  double *dx = nullptr;
-  if (hipMalloc(&dx, n * sizeof(double)) != hipSuccess) return -1;
-  unsigned long long *d = reinterpret_cast<unsigned long long *>(ctx->d_out);
+  Buf<double> dx;   // (freed on every return; that free waits for the device, so no queued copy outlives x or h)
+  if (dx.alloc(ctx, n)) return -1;
+  unsigned long long *d = reinterpret_cast<unsigned long long *>(ctx->d_out.get());
   unsigned long long h = 0;
-  bool ok = hipMemcpyAsync(dx, x, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) == hipSuccess &&
-            hipMemsetAsync(d, 0, sizeof(unsigned long long), ctx->stream) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_sqrt_check, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, dx, (long long)n, flavour, d);
-    ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
-  }
-  ok = (hipStreamSynchronize(ctx->stream) == hipSuccess) && ok;
-  ok = (hipFree(dx) == hipSuccess) && ok;
-  return ok ? (long long)h : -1;
+  if (hipMemcpyAsync(dx, x, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+      hipMemsetAsync(d, 0, sizeof(unsigned long long), ctx->stream) != hipSuccess)
+    return -1;
+  hipLaunchKernelGGL(k_sqrt_check, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, dx.get(), (long long)n, flavour, d);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess)
+    return -1;
+  return (long long)h;
 }
 
 }  // namespace svsdf_impl

@@ -33,7 +33,7 @@ EXPORTS = [
     "svsdf_group_stripe", "svsdf_set_group_serial", "svsdf_shape_selfcheck", "svsdf_mesh_section", "svsdf_mesh_section_obj",
     "svsdf_last_launches", "svsdf_set_scale", "svsdf_get_scale",
     "svsdf_frontend_set_map", "svsdf_frontend_yaw_free", "svsdf_kernel_bfs", "svsdf_astar_successors",
-    "svsdf_astar_params_default", "svsdf_astar_search", "svsdf_astar_nodes",
+    "svsdf_astar_params_default", "svsdf_astar_search", "svsdf_astar_nodes", "svsdf_debug_live_allocations",
 ]
 
 
@@ -230,6 +230,9 @@ def lib():
         L.svsdf_set_plan.argtypes = [C.c_void_p, C.POINTER(Plan)]
         L.svsdf_set_combine.argtypes = [C.c_void_p, C.c_int]
         L.svsdf_group_info.argtypes = [C.c_void_p, _ip, _ip, _ip]
+    if hasattr(L, "svsdf_debug_live_allocations"):
+        L.svsdf_debug_live_allocations.restype = C.c_longlong
+        L.svsdf_debug_live_allocations.argtypes = [C.POINTER(C.c_longlong)]
     if hasattr(L, "svsdf_group_stripe"):
         L.svsdf_group_stripe.argtypes = [C.c_void_p, C.c_int, _ip, C.POINTER(C.c_size_t), C.POINTER(Stats), C.POINTER(Plan)]
         L.svsdf_set_group_serial.argtypes = [C.c_void_p, C.c_int]
@@ -259,6 +262,12 @@ def kernel_bfs(mask, kernel_count, father_yaw):
     if rc < 0:
         raise ValueError(f"svsdf_kernel_bfs({int(mask):#x}, {kernel_count}, {father_yaw!r}) rejected its arguments ({rc})")
     return (cy.value, ki.value) if rc else None
+
+
+def live_allocations():
+    """(count, bytes) of the library's live device + pinned allocations in this process (svsdf_debug_live_allocations)."""
+    b = C.c_longlong(0)
+    return int(lib().svsdf_debug_live_allocations(C.byref(b))), int(b.value)
 
 
 def shape_id_from_inputdata(inputdata):

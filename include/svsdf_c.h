@@ -662,6 +662,10 @@ long long svsdf_debug_sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, in
  * +0 on its fast path.  The helpers decide per wave of 64 consecutive operands: one operand outside [2^-767, inf) sends
  * its whole wave through sqrt itself, so a caller that wants the fast path exercised keeps such operands apart. */
 long long svsdf_debug_sqrt_mismatches(svsdf_ctx *ctx, const double *x, size_t n, int flavour);
+/* Test hook: device plus pinned allocations this library has made in this process and not yet freed, over all contexts;
+ * *bytes (optional) their total size.  Every allocation goes through one owner type that counts; a context that has been
+ * destroyed leaves the count where it was before svsdf_create. */
+long long svsdf_debug_live_allocations(long long *bytes);
 /* Diagnostic / test: getSDFAtTimeStamp<false> (sw_manager.hpp:741-750) of n (point, time) pairs on the device, through
  * the code the solve kernels inline.  points_xy: n x 2, t: n; out8: n x 8 = sdf, pose x, y, cos(yaw), sin(yaw), body-frame
  * x, y of the point, piece-time mode (0 cumulative, 1 / 2 the reference's chain).  Under a scale schedule

@@ -96,3 +96,19 @@ def test_launch_record_abi_on_a_host_only_context(built):
     assert L.svsdf_last_launches(ctx.ctx, recs, 2, C.byref(n)) == 1          # SVSDF_ERR_INVALID
     assert L.svsdf_last_launches(None, recs, 2, C.byref(n)) == 1
     assert C.sizeof(binding.LaunchRec) == 80
+
+
+def test_host_only_context_allocates_nothing_on_the_device(built):
+    """svsdf_debug_live_allocations counts the library's device and pinned allocations: a host-only context makes none."""
+    import svsdf_amd
+    from svsdf_amd import workload
+    start = svsdf_amd.live_allocations()
+    w = workload.make("C1", P=10)
+    ctx = svsdf_amd.SvsdfContext(shape="star", head_state=w["head_state"], tail_state=w["tail_state"],
+                                 flags=svsdf_amd.FLAG_HOST_ONLY)
+    assert svsdf_amd.live_allocations() == start
+    ctx.lmbm_prepare(workload.x_from(w["q"], w["T"], svsdf_amd.backward_T))
+    assert svsdf_amd.live_allocations() == start
+    ctx.close()
+    assert svsdf_amd.live_allocations() == start
+    assert svsdf_amd.lib().svsdf_debug_live_allocations(None) == start[0]        # bytes is optional
