@@ -38,6 +38,10 @@ double shape_circumradius(int shape_id, const double *poly_xy, int nverts) {
   }
 }
 
+bool partial_finite(const double *partial, int N) {
+  return std::all_of(partial, partial + partial_doubles(N), [](double v) { return std::isfinite(v); });
+}
+
 }  // namespace
 
 extern "C" {
@@ -220,7 +224,7 @@ svsdf_ctx *svsdf_create(const svsdf_config *cfg) {
       return bail("event creation failed");
   }
   if (hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming) != hipSuccess) return bail("event creation failed");
-  if (ctx->d_traj.alloc(ctx, 1) || ctx->d_ctl.alloc_bytes(ctx, kMaxBatches * sizeof(BatchCtl) + 8 * 8 * (kMaxIter + 4)) ||
+  if (ctx->d_traj.alloc(ctx, 1) || ctx->d_ctl.alloc_bytes(ctx, kCtlBytes) ||
       ctx->d_nonfinite.alloc(ctx, 1) || ctx->d_sums.alloc(ctx, kOutPartial) || ctx->d_out.alloc(ctx, kOutDoubles) ||
       ctx->h_out.alloc(ctx, kOutDoubles) || ctx->d_ticket.alloc(ctx, 1))
     return bail("device allocation failed");
@@ -233,7 +237,7 @@ svsdf_ctx *svsdf_create(const svsdf_config *cfg) {
     (void)hipGetLastError();
   }
   // (on the context's own stream: it is non-blocking, a null-stream memset would not be ordered with its kernels)
-  if (hipMemsetAsync(ctx->d_ctl, 0, kMaxBatches * sizeof(BatchCtl) + 8 * 8 * (kMaxIter + 4), ctx->stream) != hipSuccess) return bail("hipMemset failed");
+  if (hipMemsetAsync(ctx->d_ctl, 0, kCtlBytes, ctx->stream) != hipSuccess) return bail("hipMemset failed");
   {  // shape bound radius R with sdf_shape(q) >= |q| - R for every q: the shape's circumradius about the body origin
      // (analytic, per shape; shape_circumradius above) plus the length of its offset (Shape.hpp:281-294).  The polar
      // sample of |q| - sdf(q) (k_rbound, out to 60 m) is kept as a self-check of that bound, not as its source.
@@ -327,11 +331,11 @@ int svsdf_eval_penalty_partial(svsdf_ctx *ctx, int N, const double *coeffs, cons
     dp = (ctx->combine == SVSDF_COMBINE_RCCL) ? ctx->d_red[0] : s0->d_out;
     if (ctx->combine != SVSDF_COMBINE_RCCL) {
       HIPCHK(hipSetDevice(s0->device));
-      HIPCHK(hipMemcpy(dp, ctx->comb.data(), (19 * (size_t)N + 1) * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(dp, ctx->comb.data(), (size_t)partial_doubles(N) * sizeof(double), hipMemcpyHostToDevice));
     }
   }
   if (d_partial) *d_partial = dp;
-  if (partial_len) *partial_len = 19 * (size_t)N + 1;
+  if (partial_len) *partial_len = (size_t)partial_doubles(N);
   return SVSDF_OK;
 }
 
@@ -339,8 +343,7 @@ int svsdf_accumulate_partial(svsdf_ctx *ctx, int N, const double *partial_host, 
                              double *gradT, double *gradC) {
   if (!partial_host || !cost || !gradT || !gradC || N < 1 || N > kMaxPieces)  // ctx may be NULL (pure host)
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_accumulate_partial: invalid argument");
-  for (int e = 0; e < 19 * N + 1; ++e)
-    if (!std::isfinite(partial_host[e])) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite partial");
+  if (!partial_finite(partial_host, N)) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite partial");
   accumulate(N, partial_host, cost, gradT, gradC);
   return SVSDF_OK;
 }
@@ -747,12 +750,11 @@ double svsdf_lmbm_finish(svsdf_ctx *ctx, const double *partial_host, double *g, 
   if (!ctx || !partial_host || !g || (int)ctx->xlast.size() != n) return std::numeric_limits<double>::infinity();
   const int N = (n + 3) / 4;
   const std::vector<double> &x = ctx->xlast;
-  for (int e = 0; e < 19 * N + 1; ++e)
-    if (!std::isfinite(partial_host[e])) {
-      std::fill(g, g + n, 0.0);
-      fail(ctx, SVSDF_ERR_NONFINITE, "non-finite partial");
-      return std::numeric_limits<double>::infinity();
-    }
+  if (!partial_finite(partial_host, N)) {
+    std::fill(g, g + n, 0.0);
+    fail(ctx, SVSDF_ERR_NONFINITE, "non-finite partial");
+    return std::numeric_limits<double>::infinity();
+  }
   return lmbm_complete(ctx, partial_host, x.data(), g, n);
 }
 
@@ -764,9 +766,7 @@ double svsdf_lmbm_evaluate(void *vctx, const double *x, double *g, const int n) 
   if (lmbm_prepare(ctx, x, n)) return inf;
   const int N = (n + 3) / 4;
   if (run_pipeline(ctx, N, ctx->cm.data(), ctx->T.data())) return inf;
-  const size_t plen = 19 * (size_t)N + 1;
-  for (size_t e = 0; e < plen; ++e)
-    if (!std::isfinite(ctx->h_partial[e])) return inf;
+  if (!partial_finite(ctx->h_partial, N)) return inf;
   return lmbm_complete(ctx, ctx->h_partial, x, g, n);
 }
 

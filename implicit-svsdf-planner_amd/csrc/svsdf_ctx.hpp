@@ -190,7 +190,7 @@ struct svsdf_ctx {
 
   // trajectory
   Buf<svsdf::TrajDev> d_traj;
-  svsdf_impl::Staged<double> in;   // staging, device + pinned mirror: coeffs (18N) | T (N) | tk (K) | chunk slack | chunk yaw allowance
+  svsdf_impl::Staged<double> in;   // staging, device + pinned mirror, laid out by svsdf::TrajInput
   Buf<svsdf::Pose> d_pose;
   Buf<svsdf::Chunk> d_chunks;
   size_t pose_cap = 0;
@@ -279,8 +279,8 @@ struct svsdf_ctx {
   bool icap_fitted = false;       // capacity already fitted to a measured interior count of this point set
   Buf<double> d_block_partials;
   size_t block_partials_cap = 0;  // doubles
-  Buf<double> d_sums;             // 19 * kMaxPieces + 1
-  Buf<double> d_out;              // [partial (19 * kMaxPieces + 1) | 8 x u64 stats]
+  Buf<double> d_sums;             // kOutPartial
+  Buf<double> d_out;              // [partial (kOutPartial) | svsdf::EvalCounters]
   PinBuf<double> h_out;           // pinned mirror
   double *h_out_dev = nullptr;    // the same buffer as the device addresses it (k_reduce writes the result there); null: copy
   Buf<unsigned> d_ticket;         // k_reduce: finished-block counter (zero between launches)
@@ -353,7 +353,10 @@ struct svsdf_ctx {
 namespace svsdf_impl {
 
 constexpr size_t kOutPartial = 19 * svsdf::kMaxPieces + 1;
-constexpr size_t kOutDoubles = kOutPartial + 14 + 2 * svsdf::kMaxIter;   // partial | 9 counters | solves per iteration | round scans | speculative | active per iteration | interior found | clock probe (2)
+constexpr size_t kOutDoubles = kOutPartial + sizeof(svsdf::EvalCounters) / sizeof(double);   // partial | counters row
+// the control block allocation: the batches' BatchCtl, then bytes that nothing addresses (kept: allocation sizes do not change)
+constexpr size_t kCtlUnusedTail = 8 * 8 * (svsdf::kMaxIter + 4);
+constexpr size_t kCtlBytes = svsdf::kMaxBatches * sizeof(svsdf::BatchCtl) + kCtlUnusedTail;
 constexpr int kRepeat = -12345;   // finish(): more interior points than capacity -- the arrays were grown, repeat the evaluation
 
 extern const char *kShapeNames[SVSDF_SHAPE_COUNT];

@@ -162,7 +162,7 @@ void merge_stats(svsdf_ctx *ctx) {
 
 int run_pipeline_group(svsdf_ctx *ctx, int N, const double *coeffs, const double *T) {
   const int G = (int)ctx->subs.size();
-  const size_t plen = 19 * (size_t)N + 1;
+  const size_t plen = (size_t)partial_doubles(N);
   const bool rccl = ctx->combine == SVSDF_COMBINE_RCCL;
   int rc = group_run(ctx, [&](int k) -> int {
     svsdf_ctx *s = ctx->subs[k];

@@ -22,6 +22,7 @@
 // (wave-granular dynamic work fetch), so the batches' phases overlap and fill each other's tails.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstddef>
 
 #include "svsdf_shapes.hpp"
 
@@ -136,6 +137,51 @@ struct TrajL {
 };
 
 __host__ __device__ __forceinline__ int traj_lds_doubles(int N) { return 20 * N + 1; }
+
+// ---- Buffer layouts that host and kernels share, each defined once (DESIGN.md §3 "Layouts") ----
+// The staged input block (svsdf_ctx::in, device buffer + pinned mirror; upload_traj fills it, k_prep reads it):
+//   coeffs 18N (6N x 3 column-major) | T N | tk K | chunk slack nch | chunk yaw allowance nch
+template <typename D>
+struct TrajInputT {
+  D *base;
+  int N, K;
+  __host__ __device__ __forceinline__ TrajInputT(D *b, int n, int k) : base(b), N(n), K(k) {}
+  static __host__ __device__ __forceinline__ int chunk_count(int K) { return (K + kChunk - 1) / kChunk; }   // chunks of the K-entry scan table
+  static __host__ __device__ __forceinline__ size_t doubles(int N, int K) { return 19 * (size_t)N + (size_t)K + 2 * (size_t)chunk_count(K); }
+  __host__ __device__ __forceinline__ D *coeffs() const { return base; }
+  __host__ __device__ __forceinline__ D *T() const { return base + 18 * (size_t)N; }
+  __host__ __device__ __forceinline__ D *tk() const { return base + 19 * (size_t)N; }
+  __host__ __device__ __forceinline__ D *slack() const { return tk() + K; }
+  __host__ __device__ __forceinline__ D *rot() const { return slack() + chunk_count(K); }
+};
+using TrajInput = TrajInputT<const double>;
+using TrajInputRW = TrajInputT<double>;   // (the host's pinned mirror while it is filled)
+// The partial of an evaluation: [cost | gradC 18N | gradT N]
+constexpr int kPartialGradC = 1;
+__host__ __device__ __forceinline__ int partial_gradT(int N) { return 1 + 18 * N; }
+__host__ __device__ __forceinline__ int partial_doubles(int N) { return 19 * N + 1; }
+// A block's LDS tables: [Polygon edges (kPolygonLds kernels) | pose table 4K | chunk records 4 nch | trajectory 20N+1
+// (k_solve, k_tail; k_round stages none)] doubles, rounded up to 16 bytes where per-wave state follows.
+__host__ __device__ __forceinline__ size_t block_table_doubles(int K, int N, size_t poly_edge_doubles, bool with_traj) {
+  return poly_edge_doubles + 4 * (size_t)K + 4 * (size_t)TrajInput::chunk_count(K) + (with_traj ? (size_t)traj_lds_doubles(N) : 0);
+}
+// The counters row behind the partial in d_out / h_out: finish_body writes it, the host's finish() reads it and derives the
+// next evaluation's launch plan from it.  The static_assert pins the bytes: a field may be renamed, not moved.
+struct EvalCounters {
+  unsigned long long solves, sdf_evals, scan_evals, interior_points;
+  unsigned long long nonfinite;           // non-finite per-point results
+  unsigned long long pending;             // > 0: solves the last k_round requested have not run yet
+  unsigned long long gsip_samples, gsip_iterations, culled_points;
+  unsigned long long n_solve[kMaxIter];   // solves per GSIP iteration: the host sizes the next evaluation's lane groups
+  unsigned long long round_scan_evals, speculative_evals;
+  unsigned long long n_active[kMaxIter];  // active GSIP points per iteration: the host places the fused tail (k_tail) by them
+  unsigned long long n_int;               // interior points found (may exceed the capacity: repeat)
+  unsigned long long clk[2];              // clock probe of batch 0's main solve (BatchCtl::clk)
+};
+static_assert(sizeof(EvalCounters) == (14 + 2 * kMaxIter) * 8 && offsetof(EvalCounters, n_solve) == 9 * 8 &&
+              offsetof(EvalCounters, round_scan_evals) == (9 + kMaxIter) * 8 && offsetof(EvalCounters, n_active) == (11 + kMaxIter) * 8 &&
+              offsetof(EvalCounters, n_int) == (11 + 2 * kMaxIter) * 8 && offsetof(EvalCounters, clk) == (12 + 2 * kMaxIter) * 8,
+              "EvalCounters: the counters row keeps its bytes");
 
 // lds must hold 20N+1 doubles: T[N] | S[N+1] | c[18N]
 __device__ __forceinline__ TrajL stage_traj(const TrajDev *__restrict__ g, double *lds) {
@@ -542,7 +588,8 @@ __global__ void __launch_bounds__(1024) k_prep(const double *__restrict__ in, in
                        int nbatch, int *__restrict__ nonfinite) {
   extern __shared__ double prep_lds[];
   if (threadIdx.x == 0 && nonfinite) *nonfinite = 0;   // (was a memset node of its own in front of every evaluation)
-  const double *coeffs = in, *T = in + 18 * N, *tk = in + 19 * N, *slack = in + 19 * N + K;
+  const TrajInput inp(in, N, K);
+  const double *coeffs = inp.coeffs(), *T = inp.T(), *tk = inp.tk(), *slack = inp.slack();
   for (int b = threadIdx.x; b < nbatch; b += blockDim.x) {
     BatchCtl &c = ctl[b];
     for (int r = 0; r < kMaxIter + 2; ++r) { c.n_active[r] = 0; c.n_solve[r] = 0; c.n_seed[r] = 0; }
@@ -578,7 +625,7 @@ __global__ void __launch_bounds__(1024) k_prep(const double *__restrict__ in, in
   }
   __threadfence_block();
   __syncthreads();
-  const int nch = (K + kChunk - 1) / kChunk;
+  const int nch = TrajInput::chunk_count(K);
   for (int c = threadIdx.x; c < nch; c += blockDim.x) {
     const int k0 = c * kChunk, k1 = (k0 + kChunk < K) ? k0 + kChunk : K;
     double xmin = pose[k0].x, xmax = xmin, ymin = pose[k0].y, ymax = ymin;
@@ -1550,7 +1597,7 @@ k_solve(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Po
   const long long total = qs_total(qs, n);
   if (total <= 0 || (long long)blockIdx.x * (((prune & 2) != 0) ? (blockDim.x >> 6) : (blockDim.x / G)) >= total) return;
   const int K = trg->K;
-  const int nch = (K + kChunk - 1) / kChunk;
+  const int nch = (K + kChunk - 1) / kChunk;   // (TrajInput::chunk_count written out: the call moved this kernel's register allocation)
   stage_poly_edges<SHAPE>(sp, solve_lds);
   double *tab_lds = solve_lds + poly_lds_doubles<SHAPE>(sp.nverts);
   Pose *pose = reinterpret_cast<Pose *>(tab_lds);
@@ -1563,7 +1610,7 @@ k_solve(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Po
   }
   const TrajL tr = stage_traj(trg, tab_lds + 4 * (size_t)K + 4 * (size_t)nch);  // ends with __syncthreads
   // per-wave descent state behind the trajectory (16-byte aligned: the tables before it are whole doubles, rounded up)
-  const size_t tables = poly_lds_doubles<SHAPE>(sp.nverts) + 4 * (size_t)K + 4 * (size_t)nch + (size_t)traj_lds_doubles(tr.N);
+  const size_t tables = poly_lds_doubles<SHAPE>(sp.nverts) + 4 * (size_t)K + 4 * (size_t)nch + (size_t)traj_lds_doubles(tr.N);   // = block_table_doubles
   char *wave_lds = reinterpret_cast<char *>(solve_lds + ((tables + 1) & ~(size_t)1)) + (threadIdx.x >> 6) * ladder_lds_bytes(G);
   const int li = Grp<G>::li();
   unsigned n_eval = 0, n_scan = 0, n_solved = 0, n_culled = 0, n_spec = 0;
@@ -2472,7 +2519,7 @@ k_round(const TrajDev *__restrict__ trg, const Pose *__restrict__ pose_g,
   const unsigned long long t_wave0 = SVSDF_SITE_CLOCK();
   unsigned long long tfl = t_wave0;
   const int K = trg->K;
-  const int nch = (K + kChunk - 1) / kChunk;
+  const int nch = TrajInput::chunk_count(K);
   stage_poly_edges<SHAPE>(sp, round_lds);
   double *tab_lds = round_lds + poly_lds_doubles<SHAPE>(sp.nverts);
   Pose *pose = reinterpret_cast<Pose *>(tab_lds);
@@ -2694,7 +2741,7 @@ k_tail(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Pos
   const int wave_g = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
   if (n_act <= 0 || (int)blockIdx.x * (kTailBlock / 64) * ppw >= n_act) return;   // block-uniform
   const int K = trg->K;
-  const int nch = (K + kChunk - 1) / kChunk;
+  const int nch = (K + kChunk - 1) / kChunk;   // (TrajInput::chunk_count written out: the call moved this kernel's register allocation)
   stage_poly_edges<SHAPE>(sp, tail_lds);
   double *tab_lds = tail_lds + poly_lds_doubles<SHAPE>(sp.nverts);
   Pose *pose = reinterpret_cast<Pose *>(tab_lds);
@@ -2706,7 +2753,7 @@ k_tail(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Pos
     for (int i = threadIdx.x; i < 4 * nch; i += blockDim.x) tab_lds[4 * (size_t)K + i] = srcc[i];
   }
   const TrajL tr = stage_traj(trg, tab_lds + 4 * (size_t)K + 4 * (size_t)nch);  // ends with __syncthreads (the only block barrier)
-  const size_t tables = poly_lds_doubles<SHAPE>(sp.nverts) + 4 * (size_t)K + 4 * (size_t)nch + (size_t)traj_lds_doubles(tr.N);
+  const size_t tables = poly_lds_doubles<SHAPE>(sp.nverts) + 4 * (size_t)K + 4 * (size_t)nch + (size_t)traj_lds_doubles(tr.N);   // = block_table_doubles
   const bool local = it0 == 0 && (clist_on & 4) != 0;   // (bit 2 of clist_on: the host's switch, SVSDF_TAIL_LOCAL=0 turns it off; see below)
   // per-wave stride: the wave-local GSIP block (the last part of a wave's region) only exists when it is used (launch_tail
   // sizes the launch's LDS the same way)
@@ -2968,7 +3015,7 @@ __device__ __forceinline__ bool assemble_terms(const TrajL &tr, const double *__
 // doubles of LDS behind the trajectory that the one-block form of the assembly uses: the sums [plen], the terms of the
 // block's points term-major [20][kBlock], and per wave the lane masks of the active points and of every piece [N + 1] (64-bit)
 __host__ __device__ __forceinline__ size_t assemble_small_doubles(int N) {
-  return (size_t)(19 * N + 1) + 20 * (size_t)kBlock + (size_t)(kBlock / 64) * (size_t)(N + 1);
+  return (size_t)partial_doubles(N) + 20 * (size_t)kBlock + (size_t)(kBlock / 64) * (size_t)(N + 1);
 }
 
 template <bool SC = false>
@@ -2986,7 +3033,7 @@ __device__ __forceinline__ void assemble_body(const TrajDev *__restrict__ trg, c
   // order (k_final).  Morton-sorted neighbours share their piece, so a wave sees 1-3 distinct ids per step.
   const TrajL tr = stage_traj(trg, asm_lds);
   const int N = tr.N;
-  const int plen = 19 * N + 1;
+  const int plen = partial_doubles(N);
   constexpr int kWaves = kBlock / 64;
   double *acc_all = asm_lds + traj_lds_doubles(N);
   const int lane = (int)(threadIdx.x & 63);
@@ -3101,10 +3148,12 @@ k_final(const double *__restrict__ block_partials, int nblocks, double *__restri
 __device__ __forceinline__ void finish_body(const double *__restrict__ sums, int N, double *__restrict__ partial,
                                             const BatchCtl *__restrict__ ctl, int nbatch, int it_end,
                                             const int *__restrict__ nonfinite, unsigned long long *__restrict__ stats_out) {
-  for (int k = threadIdx.x; k <= 18 * N; k += blockDim.x) partial[k] = sums[k];
+  EvalCounters *const cnt = reinterpret_cast<EvalCounters *>(stats_out);
+  const int gT = partial_gradT(N);
+  for (int k = threadIdx.x; k < gT; k += blockDim.x) partial[k] = sums[k];
   if (threadIdx.x == 0) {
     double suf = 0.0;
-    for (int j = N - 1; j >= 0; --j) { partial[1 + 18 * N + j] = suf; suf += sums[1 + 18 * N + j]; }
+    for (int j = N - 1; j >= 0; --j) { partial[gT + j] = suf; suf += sums[gT + j]; }
   }
   if (threadIdx.x < 64) {
     // the counters, gathered by the first wave (round 5: one thread used to walk nbatch x 32 slots x 6 words and three
@@ -3134,8 +3183,8 @@ __device__ __forceinline__ void finish_body(const double *__restrict__ sums, int
       iters = (oi > iters) ? oi : iters;
     }
     if (lane < kMaxIter) {
-      stats_out[9 + lane] = ns;                  // solves per GSIP iteration: the host sizes the next evaluation's lane groups
-      stats_out[11 + kMaxIter + lane] = na;      // active GSIP points per iteration: the host places the fused tail (k_tail) by them
+      cnt->n_solve[lane] = ns;
+      cnt->n_active[lane] = na;
     }
     if (lane == 0) {
       unsigned long long in = 0, nf = (unsigned long long)__hip_atomic_load(nonfinite, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), rem = 0;
@@ -3143,13 +3192,13 @@ __device__ __forceinline__ void finish_body(const double *__restrict__ sums, int
         in += (unsigned long long)ctl[b].n_active[0]; nf += (unsigned long long)ctl[b].nonfinite;
         rem += (unsigned long long)ctl[b].n_solve[it_end];    // > 0: solves requested but not run yet
       }
-      stats_out[0] = so; stats_out[1] = ev; stats_out[2] = sc; stats_out[3] = in; stats_out[4] = nf;
-      stats_out[5] = rem; stats_out[6] = seeded; stats_out[7] = iters; stats_out[8] = cu;
-      stats_out[9 + kMaxIter] = rs;
-      stats_out[10 + kMaxIter] = sp_;
-      stats_out[11 + 2 * kMaxIter] = (unsigned long long)ctl[0].n_int;   // interior points found (may exceed the capacity: repeat)
-      stats_out[12 + 2 * kMaxIter] = ctl[0].clk[0];                       // clock probe of batch 0's main solve (BatchCtl::clk)
-      stats_out[13 + 2 * kMaxIter] = ctl[0].clk[1];
+      cnt->solves = so; cnt->sdf_evals = ev; cnt->scan_evals = sc; cnt->interior_points = in; cnt->nonfinite = nf;
+      cnt->pending = rem; cnt->gsip_samples = seeded; cnt->gsip_iterations = iters; cnt->culled_points = cu;
+      cnt->round_scan_evals = rs;
+      cnt->speculative_evals = sp_;
+      cnt->n_int = (unsigned long long)ctl[0].n_int;
+      cnt->clk[0] = ctl[0].clk[0];
+      cnt->clk[1] = ctl[0].clk[1];
     }
   }
 }
@@ -3157,7 +3206,7 @@ __device__ __forceinline__ void finish_body(const double *__restrict__ sums, int
 // What the host reads of a result row [sums (19 kMaxPieces + 1) | counters]: the 19 N + 1 sums in use and the counters.
 __device__ __forceinline__ void copy_result_to_host(double *__restrict__ host_out, const double *__restrict__ out, int N,
                                                     int out_partial, int out_doubles) {
-  const int plen = 19 * N + 1;
+  const int plen = partial_doubles(N);
   for (int k = threadIdx.x; k < plen; k += blockDim.x) host_out[k] = out[k];
   for (int k = out_partial + threadIdx.x; k < out_doubles; k += blockDim.x) host_out[k] = out[k];
 }
@@ -3203,7 +3252,7 @@ k_reduce(const TrajDev *__restrict__ trg, const double *__restrict__ px_, const 
   assemble_body<SC>(trg, px_, py_, P, res_sdf, res_t, res_gx, res_gy, safety_hor, weight_p, block_partials, nonfinite, asm_lds, fuse && one_block, scl);
   if (!fuse) return;
   const int N = trg->N;
-  const int plen = 19 * N + 1;
+  const int plen = partial_doubles(N);
   const int nblocks = (int)gridDim.x;
   double *sums = asm_lds + traj_lds_doubles(N);   // (the accumulator rows are free again: plen <= 4 plen doubles)
   if (!one_block) {

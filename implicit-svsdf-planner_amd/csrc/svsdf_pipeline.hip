@@ -182,16 +182,61 @@ void launch_k_yaw_free(hipStream_t st, const unsigned long long *occ, int row_wo
 }  // namespace svsdf
 namespace svsdf_impl {
 
-// Persistent-grid launcher of the argmin kernel.  max_queries bounds the (possibly device-side)
-// query count and sizes the grid; surplus blocks exit before touching LDS.
-size_t table_lds_doubles(const svsdf_ctx *ctx) {
-  return 4 * (size_t)ctx->K + 4 * (size_t)((ctx->K + kChunk - 1) / kChunk);
+// Brackets a launch with a pair of profile events and appends the pair to `list`; nothing without per-launch profiling.
+struct ProfileSpan {
+  svsdf_ctx *ctx; hipStream_t st; std::vector<std::pair<size_t, size_t>> &list; size_t e0 = 0;
+  ProfileSpan(svsdf_ctx *c, hipStream_t s, std::vector<std::pair<size_t, size_t>> &l) : ctx(c), st(s), list(l) {
+    if (ctx->profile) { e0 = next_event(ctx); (void)hipEventRecord(ctx->ev_pool[e0], st); }
+  }
+  ~ProfileSpan() {
+    if (ctx->profile) { const size_t e1 = next_event(ctx); (void)hipEventRecord(ctx->ev_pool[e1], st); list.emplace_back(e0, e1); }
+  }
+};
+// a launch that could not be made leaves its text in launch_err (the first one stays; join_batches reports it)
+static void launch_result(svsdf_ctx *ctx, bool launched, const char *kernel) {
+  if (!launched && ctx->launch_err.empty()) ctx->launch_err = std::string(kernel) + ": shape not compiled into this build";
+}
+static void lds_too_long(svsdf_ctx *ctx, const std::string &what) {
+  if (ctx->launch_err.empty()) ctx->launch_err = "trajectory too long for the LDS pose table (" + what + ")";
+}
+// GSIP selection of k_round / k_tail: band `sel` below the best bound, every sample from iteration `all_it` on.
+// The seed bound of the scanning modes is tight: a narrow band selects (ctx->scan_delta: 0.002 m, solve-all from
+// iteration 7); the chunk bound of the cheap mode needs 0.1 m / iteration 5.  SVSDF_SELECT_DELTA overrides both.
+struct GsipSelect { double sel; int all_it; };
+static GsipSelect gsip_select(const svsdf_ctx *ctx, int mode) {
+  const bool scans = mode != 0;
+  return {(scans && !ctx->select_env) ? ctx->scan_delta : ctx->select_delta, (scans && !ctx->all_iter_env) ? 7 : ctx->delta_all_iter};
 }
 
+// Dynamic LDS of one block (svsdf::block_table_doubles): the tables -- a Polygon's edges in front of them while the block
+// still fits, else the kernel variant that reads the edges from global memory (`fall_back`) -- and behind them, 16-byte
+// aligned, `per_wave` bytes of state for each wave of the block.  k_solve's block size is chosen here, from the table bytes
+// (`block`); k_tail's is fixed.  k_round stages no trajectory, has no per-wave state and < 16 KB of static tables that count
+// against the block's budget.
+enum class TableUser { Solve, Round, Tail };
+struct BlockLds { size_t bytes = 0; int block = 0; bool poly_lds = false, fits = false; };
+static BlockLds plan_block_lds(const svsdf_ctx *ctx, TableUser user, size_t per_wave, bool poly_lds, bool fall_back = true) {
+  BlockLds r;
+  for (r.poly_lds = poly_lds;; r.poly_lds = false) {
+    const size_t lds = block_table_doubles(ctx->K, ctx->N, r.poly_lds ? (size_t)svsdf::kPolyEdgeDoubles * (size_t)ctx->sp.nverts : 0,
+                                           user != TableUser::Round) * sizeof(double);
+    r.block = (user == TableUser::Solve) ? ctx->block : (user == TableUser::Tail) ? kTailBlock : kRoundBlock;
+    if (user == TableUser::Solve && !ctx->block_env)
+      r.block = ((lds + per_wave) * 12 <= 160 * 1024) ? 64 : ((lds + 2 * per_wave) * 6 <= 160 * 1024) ? 128 : 256;
+    r.bytes = (user == TableUser::Round) ? lds : ((lds + 15) & ~(size_t)15) + (size_t)(r.block / 64) * per_wave;
+    r.fits = r.bytes + (user == TableUser::Round ? 16384 : 0) <= ctx->lds_limit;
+    if (r.fits || !r.poly_lds || !fall_back) return r;
+  }
+}
+// k_tail: a wave's state, with the wave-local copy of the GSIP state or without
+static size_t tail_wave_bytes(bool local) { return local ? kTailWaveLds : kTailWaveLds - kTailLocalBytes; }
+
+// Persistent-grid launcher of the argmin kernel.  max_queries bounds the (possibly device-side)
+// query count and sizes the grid; surplus blocks exit before touching LDS.
 void launch_solve(svsdf_ctx *ctx, int G, hipStream_t st, const QuerySet &qs, long long max_queries, double *out_sdf,
                   double *out_t, BatchCtl *ctl, int work_idx,
                   double cull_thresh = std::numeric_limits<double>::infinity()) {
-  const double *d_tk = ctx->in.d + 19 * (size_t)ctx->N;
+  const TrajInput in(ctx->in.d, ctx->N, ctx->K);
   if (ctx->scaled) {
     // the scaled path (§4c): its widths only, and no cull -- both culls bound the rigid map, not the scaled descent's value
     G = scaled_lanes(G);
@@ -207,69 +252,39 @@ void launch_solve(svsdf_ctx *ctx, int G, hipStream_t st, const QuerySet &qs, lon
   // A Polygon's edges go in front of the tables while the whole block still fits the device's per-block LDS; a long
   // trajectory (large pose table) falls back to the kernel variant that reads the edges from global memory.
   const size_t wlds = ladder_lds_bytes(G);   // per wave: the descent state of its 64 / G groups
-  bool poly_lds = ctx->poly_lds;
-  size_t lds = 0, lds_total = 0;
-  int blk = ctx->block;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    lds = (table_lds_doubles(ctx) + (size_t)traj_lds_doubles(ctx->N) + (poly_lds ? (size_t)svsdf::kPolyEdgeDoubles * (size_t)ctx->sp.nverts : 0)) * sizeof(double);
-    blk = ctx->block;
-    if (!ctx->block_env) blk = ((lds + wlds) * 12 <= 160 * 1024) ? 64 : ((lds + 2 * wlds) * 6 <= 160 * 1024) ? 128 : 256;
-    lds_total = ((lds + 15) & ~(size_t)15) + (size_t)(blk / 64) * wlds;
-    if (lds_total <= ctx->lds_limit || !poly_lds) break;
-    poly_lds = false;
-  }
-  if (lds_total > ctx->lds_limit) {
-    if (ctx->launch_err.empty()) ctx->launch_err = "trajectory too long for the LDS pose table (" + std::to_string(lds_total) + " B of " + std::to_string(ctx->lds_limit) + " B per block)";
-    return;
-  }
+  const BlockLds l = plan_block_lds(ctx, TableUser::Solve, wlds, ctx->poly_lds);
+  const int blk = l.block;
+  if (!l.fits) return lds_too_long(ctx, std::to_string(l.bytes) + " B of " + std::to_string(ctx->lds_limit) + " B per block");
   const unsigned grid = (unsigned)std::min<long long>((lanes + blk - 1) / blk, (long long)(256 * ctx->waves_per_cu * 64) / blk);
-  size_t e0 = 0, e1 = 0;
-  if (ctx->profile) { e0 = next_event(ctx); (void)hipEventRecord(ctx->ev_pool[e0], st); }
   // (the second, value-based cull runs with the first one: main points of an evaluation that may cull)
   const bool cull2 = std::isfinite(cull_thresh) && ctx->cull2;
-  const double *d_rot = d_tk + ctx->K + (ctx->K + kChunk - 1) / kChunk;
-  const SolveLaunch a{ctx->d_traj, d_tk, ctx->d_pose, ctx->d_chunks, ctx->sp, qs, out_sdf, out_t, ctx->prune | (solo ? 2 : 0) | (ctx->ltab_mode >= 2 ? 4 : 0) | (ctx->ltab_mode >= 3 ? 8 : 0), ctl, work_idx, cull_thresh,
-                      cull2 ? d_rot : nullptr, ctx->slack_max, ctx->scaled ? &ctx->scale : nullptr, ctx->d_ltab};
-  const int shape = poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
-  if (!launch_k_solve(shape, G, grid, (unsigned)blk, lds_total, st, a) && ctx->launch_err.empty())
-    ctx->launch_err = "k_solve: shape not compiled into this build";
-  if (svsdf_launch_rec *r = record_launch(ctx, ctx->scaled ? SVSDF_KERNEL_SOLVE_SCALED : SVSDF_KERNEL_SOLVE, compiled_shape(shape), grid, (unsigned)blk, lds_total, max_queries,
-                                          (int)(ctl - ctx->d_ctl))) {
-    r->targ[0] = G; r->targ[1] = 1; r->iter = work_idx; r->solo = solo ? 1 : 0;
-  }
-  debug_sync(st, "k_solve", G, work_idx);
-  if (ctx->profile) {
-    e1 = next_event(ctx);
-    (void)hipEventRecord(ctx->ev_pool[e1], st);
-    ctx->refine_events.emplace_back(e0, e1);
+  const SolveLaunch a{ctx->d_traj, in.tk(), ctx->d_pose, ctx->d_chunks, ctx->sp, qs, out_sdf, out_t, ctx->prune | (solo ? 2 : 0) | (ctx->ltab_mode >= 2 ? 4 : 0) | (ctx->ltab_mode >= 3 ? 8 : 0), ctl, work_idx, cull_thresh,
+                      cull2 ? in.rot() : nullptr, ctx->slack_max, ctx->scaled ? &ctx->scale : nullptr, ctx->d_ltab};
+  const int shape = l.poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
+  {
+    const ProfileSpan span(ctx, st, ctx->refine_events);
+    launch_result(ctx, launch_k_solve(shape, G, grid, (unsigned)blk, l.bytes, st, a), "k_solve");
+    if (svsdf_launch_rec *r = record_launch(ctx, ctx->scaled ? SVSDF_KERNEL_SOLVE_SCALED : SVSDF_KERNEL_SOLVE, compiled_shape(shape), grid, (unsigned)blk, l.bytes, max_queries,
+                                            (int)(ctl - ctx->d_ctl))) {
+      r->targ[0] = G; r->targ[1] = 1; r->iter = work_idx; r->solo = solo ? 1 : 0;
+    }
+    debug_sync(st, "k_solve", G, work_idx);
   }
   ctx->stats.solve_launches++;
 }
 
 void launch_round(svsdf_ctx *ctx, hipStream_t st, int b, int it) {
   const int mode = bound_mode_of(ctx);   // k_round MODE: cheap / full / lazy / anchor bound
-  const bool scans = mode != 0;
   const long long pts = std::max(1, ctx->bcount[b]);
-  bool poly_lds = ctx->poly_lds;
-  size_t lds = (table_lds_doubles(ctx) + (poly_lds ? (size_t)svsdf::kPolyEdgeDoubles * (size_t)ctx->sp.nverts : 0)) * sizeof(double);
-  if (lds + 16384 > ctx->lds_limit && poly_lds) {   // (k_round's static tables: < 16 KB) edges from global memory instead
-    poly_lds = false;
-    lds = table_lds_doubles(ctx) * sizeof(double);
-  }
-  if (lds + 16384 > ctx->lds_limit) {
-    if (ctx->launch_err.empty()) ctx->launch_err = "trajectory too long for the LDS pose table (k_round)";
-    return;
-  }
+  const BlockLds l = plan_block_lds(ctx, TableUser::Round, 0, ctx->poly_lds);
+  if (!l.fits) return lds_too_long(ctx, "k_round");
   // late iterations hold few points and are latency-bound: request every sample there, which
   // avoids supplementary iterations at no cost in time
-  // the seed bound of the scanning modes is tight: a narrow band selects (ctx->scan_delta: 0.002 m, solve-all from
-  // iteration 7); the chunk bound of the cheap mode needs 0.1 m / iteration 5.  SVSDF_SELECT_DELTA overrides both.
-  const double sel = (scans && !ctx->select_env) ? ctx->scan_delta : ctx->select_delta;
-  const int all_it = (scans && !ctx->all_iter_env) ? 7 : ctx->delta_all_iter;
+  const GsipSelect gsel = gsip_select(ctx, mode);
   // the scaled path (§4c) requests every sample in every iteration: the bounds are values of the RIGID table, and a scaled
   // solve from a rigid seed is bounded by none of them
-  const double delta = (it >= all_it || ctx->scaled) ? 1e300 : sel;
-  const double band_delta = (it >= all_it || ctx->scaled) ? 1e300 : ctx->select_delta;   // lazy mode: cheap-bound band that gets scanned
+  const double delta = (it >= gsel.all_it || ctx->scaled) ? 1e300 : gsel.sel;
+  const double band_delta = (it >= gsel.all_it || ctx->scaled) ? 1e300 : ctx->select_delta;   // lazy mode: cheap-bound band that gets scanned
   // iterations 0 and 1 are (almost always) GSIP rounds 1 and 2 with 2 and 6 samples: 8 lanes per point; later rounds have
   // 18-21 samples: 32 lanes per point (either handles any count).  Iteration 2 (18 samples, still every interior point
   // active: throughput, not latency) also runs faster with 8 lanes and three sample passes per point -- measured round 3,
@@ -280,80 +295,52 @@ void launch_round(svsdf_ctx *ctx, hipStream_t st, int b, int it) {
   const unsigned grid = (unsigned)std::min<long long>((pts * lp + kRoundBlock - 1) / kRoundBlock, (long long)ctx->n_cu * ctx->round_blocks_per_cu);
   const RoundLaunch a{ctx->d_traj, ctx->d_pose, ctx->d_chunks, ctx->sp, ctx->d_px, ctx->d_py, ctx->gs, ctx->icap, it, delta,
                       band_delta, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy, ctx->d_ctl + b, ctx->round_list | ((ctx->scan_anchors && ctx->lipschitz_ok) ? 16 : 0)};
-  size_t e0 = 0, e1 = 0;
-  if (ctx->profile) { e0 = next_event(ctx); (void)hipEventRecord(ctx->ev_pool[e0], st); }
-  const int shape = poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
-  if (!launch_k_round(shape, lp, mode, grid, lds, st, a) && ctx->launch_err.empty())
-    ctx->launch_err = "k_round: shape not compiled into this build";
-  if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_ROUND, compiled_shape(shape), grid, (unsigned)kRoundBlock, lds, pts, b)) {
+  const int shape = l.poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
+  const ProfileSpan span(ctx, st, ctx->round_events);
+  launch_result(ctx, launch_k_round(shape, lp, mode, grid, l.bytes, st, a), "k_round");
+  if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_ROUND, compiled_shape(shape), grid, (unsigned)kRoundBlock, l.bytes, pts, b)) {
     r->targ[0] = lp; r->targ[1] = mode; r->iter = it; r->anchors = (a.clist_on & 16) ? 1 : 0;
   }
   debug_sync(st, "k_round", lp * 10 + mode, it);
-  if (ctx->profile) {
-    e1 = next_event(ctx);
-    (void)hipEventRecord(ctx->ev_pool[e1], st);
-    ctx->round_events.emplace_back(e0, e1);
-  }
-}
-
-// LDS one k_tail block asks for (Polygon edges in LDS or not), and whether the device grants it
-size_t tail_lds_bytes(const svsdf_ctx *ctx, bool poly_lds, bool local) {
-  const size_t lds_tables = ((table_lds_doubles(ctx) + (size_t)traj_lds_doubles(ctx->N) + (poly_lds ? (size_t)svsdf::kPolyEdgeDoubles * (size_t)ctx->sp.nverts : 0)) * sizeof(double) + 15) & ~(size_t)15;
-  return lds_tables + (kTailBlock / 64) * (local ? kTailWaveLds : kTailWaveLds - kTailLocalBytes);
 }
 
 // k_tail: every GSIP iteration of batch b from `it0` on, in one launch (two points per wave, solved in the wave).
 void launch_tail(svsdf_ctx *ctx, hipStream_t st, int b, int it0) {
   const int mode = bound_mode_of(ctx);
-  const bool scans = mode != 0;
-  const double sel = (scans && !ctx->select_env) ? ctx->scan_delta : ctx->select_delta;
-  const int all_it = (scans && !ctx->all_iter_env) ? 7 : ctx->delta_all_iter;
-  const int all_after = (ctx->tail_all_after < 0) ? std::max(0, all_it - it0) : ctx->tail_all_after;
+  const GsipSelect gsel = gsip_select(ctx, mode);
+  const int all_after = (ctx->tail_all_after < 0) ? std::max(0, gsel.all_it - it0) : ctx->tail_all_after;
   // the active count lives on the device; the grid is sized by what the previous evaluation had there (surplus blocks
   // exit at once, missing ones are made up for by the waves' work fetch)
   long long pts = std::max(1, ctx->bcount[b]);
   if (ctx->have_prev_nactive && it0 <= ctx->prev_tail_iter && it0 < kMaxIter)
     pts = std::min<long long>(pts, ctx->prev_nactive[it0] / std::max(1, ctx->nbatch) * 5 / 4 + 64);
-  bool poly_lds = ctx->poly_lds;
   // the wave-local copy of the GSIP state only where it is used: the whole loop in the tail (it0 == 0) with the switch on;
-  // when it does not fit, the state stays in global memory (same bits)
+  // when it does not fit, the state stays in global memory (same bits) -- that goes first, then the Polygon's edges
   bool local = ctx->tail_local && it0 == 0;
-  size_t lds = 0;
-  for (int attempt = 0; attempt < 4; ++attempt) {
-    lds = tail_lds_bytes(ctx, poly_lds, local);
-    if (lds <= ctx->lds_limit) break;
-    if (local) local = false;
-    else if (poly_lds) poly_lds = false;
-    else break;
+  BlockLds l = plan_block_lds(ctx, TableUser::Tail, tail_wave_bytes(local), ctx->poly_lds, !local);
+  if (!l.fits && local) {
+    local = false;
+    l = plan_block_lds(ctx, TableUser::Tail, tail_wave_bytes(false), ctx->poly_lds);
   }
-  if (lds > ctx->lds_limit) {
-    if (ctx->launch_err.empty()) ctx->launch_err = "trajectory too long for the LDS pose table (k_tail)";
-    return;
-  }
+  if (!l.fits) return lds_too_long(ctx, "k_tail");
   // one point per wave while that still fits the chip's wave slots (3 per SIMD): the launch is a latency chain then
   const int ppw = (pts <= (long long)ctx->n_cu * 12) ? 1 : 2;
   const long long per_block = (kTailBlock / 64) * ppw;
   const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((pts + per_block - 1) / per_block, (long long)ctx->n_cu * 3));
-  const double *d_tk = ctx->in.d + 19 * (size_t)ctx->N;
-  const TailLaunch a{ctx->d_traj, d_tk, ctx->d_pose, ctx->d_chunks, ctx->sp, ctx->d_px, ctx->d_py, ctx->gs, ctx->icap, it0, mode,
-                     sel, ctx->select_delta, all_after, ppw, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
+  const TailLaunch a{ctx->d_traj, TrajInput(ctx->in.d, ctx->N, ctx->K).tk(), ctx->d_pose, ctx->d_chunks, ctx->sp, ctx->d_px, ctx->d_py, ctx->gs, ctx->icap, it0, mode,
+                     gsel.sel, ctx->select_delta, all_after, ppw, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
                      ctx->d_ctl + b, ctx->round_list | (local ? 4 : 0) | (ctx->tail_duo ? 0 : 8) | ((ctx->scan_anchors && ctx->lipschitz_ok) ? 16 : 0), ctx->prune,
                      // a wave slot for every point at two waves per SIMD: the instantiation without scratch (k_tail, kTailLatencyWaves)
                      (ctx->tail_latency && ppw == 1 && pts <= (long long)ctx->n_cu * 4 * svsdf::kTailLatencyWaves) ? 1 : 0};
-  size_t e0 = 0, e1 = 0;
-  if (ctx->profile) { e0 = next_event(ctx); (void)hipEventRecord(ctx->ev_pool[e0], st); }
-  const int shape = poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
-  if (!launch_k_tail(shape, mode, grid, lds, st, a) && ctx->launch_err.empty())
-    ctx->launch_err = "k_tail: shape not compiled into this build";
-  if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_TAIL, compiled_shape(shape), grid, (unsigned)kTailBlock, lds, pts, b)) {
-    r->targ[0] = mode; r->targ[1] = a.latency ? svsdf::kTailLatencyWaves : SVSDF_TAIL_WAVES; r->iter = it0; r->points_per_wave = ppw;
-    r->local_state = local ? 1 : 0; r->duo = (ppw == 1 && ctx->tail_duo) ? 1 : 0; r->anchors = (a.clist_on & 16) ? 1 : 0;
-  }
-  debug_sync(st, "k_tail", mode, it0);
-  if (ctx->profile) {
-    e1 = next_event(ctx);
-    (void)hipEventRecord(ctx->ev_pool[e1], st);
-    ctx->tail_events.emplace_back(e0, e1);
+  const int shape = l.poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
+  {
+    const ProfileSpan span(ctx, st, ctx->tail_events);
+    launch_result(ctx, launch_k_tail(shape, mode, grid, l.bytes, st, a), "k_tail");
+    if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_TAIL, compiled_shape(shape), grid, (unsigned)kTailBlock, l.bytes, pts, b)) {
+      r->targ[0] = mode; r->targ[1] = a.latency ? svsdf::kTailLatencyWaves : SVSDF_TAIL_WAVES; r->iter = it0; r->points_per_wave = ppw;
+      r->local_state = local ? 1 : 0; r->duo = (ppw == 1 && ctx->tail_duo) ? 1 : 0; r->anchors = (a.clist_on & 16) ? 1 : 0;
+    }
+    debug_sync(st, "k_tail", mode, it0);
   }
   ctx->stats.tail_launches++;
 }
@@ -371,7 +358,7 @@ int choose_tail_iter(const svsdf_ctx *ctx) {
   if (ctx->tail_mode == -2 || ctx->scaled) return -1;   // (the scaled path runs the launch chain only, §4c)
   //  a trajectory whose tables leave no room for the tail's per-wave state runs the launch chain, which needs
   // less LDS per block, instead of failing the evaluation (128 pieces on a device with 64 KB per block)
-  if (tail_lds_bytes(ctx, false, false) > ctx->lds_limit) return -1;
+  if (!plan_block_lds(ctx, TableUser::Tail, tail_wave_bytes(false), false).fits) return -1;
   if (ctx->tail_mode >= 0) return std::min(ctx->tail_mode, (int)kMaxIter - 2);
   if (!ctx->have_prev_nactive) return -1;   // first evaluation of a point set: the interior count is not known yet
   const long long below = ctx->tail_below > 0 ? ctx->tail_below : (long long)ctx->n_cu * 24;
@@ -384,8 +371,7 @@ void launch_classify(svsdf_ctx *ctx, hipStream_t st, int b) {
   const ClassifyLaunch a{ctx->d_traj, ctx->sp, ctx->d_px, ctx->d_py, ctx->d_sdf, ctx->d_t, ctx->d_res_sdf, ctx->d_res_t,
                          ctx->d_res_gx, ctx->d_res_gy, ctx->gs, ctx->d_ctl + b, &ctx->d_ctl->n_int, (int)ctx->icap,
                          ctx->scaled ? &ctx->scale : nullptr};
-  if (!launch_k_classify(ctx->cfg.shape_id, grid, lds, st, a) && ctx->launch_err.empty())
-    ctx->launch_err = "k_classify: shape not compiled into this build";
+  launch_result(ctx, launch_k_classify(ctx->cfg.shape_id, grid, lds, st, a), "k_classify");
   (void)record_launch(ctx, ctx->scaled ? SVSDF_KERNEL_CLASSIFY_SCALED : SVSDF_KERNEL_CLASSIFY, compiled_shape(ctx->cfg.shape_id), grid,
                       (unsigned)kBlock, lds, ctx->bcount[b], b);
   debug_sync(st, "k_classify", b, 0);
@@ -410,7 +396,7 @@ int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bo
   size_t K = 0;
   for (double t = 0.0; t <= dur; t += 0.15) ++K;
   if (K < 1 || K > 16000) return fail(ctx, SVSDF_ERR_INVALID, "trajectory duration out of range for the scan table");
-  const size_t need = 19 * (size_t)N + K + 2 * ((K + kChunk - 1) / kChunk);  // coeffs | T | tk | chunk slack | chunk yaw allowance
+  const size_t need = TrajInput::doubles(N, (int)K);
   if (need > ctx->in.cap) {
     int rc = ctx->in.reserve(ctx, need + 4096);
     if (rc) return rc;
@@ -422,15 +408,16 @@ int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bo
     if (rc) return rc;
     ctx->pose_cap = K + 1024;
   }
-  std::memcpy(ctx->in.h, coeffs, sizeof(double) * 18 * N);
-  std::memcpy(ctx->in.h + 18 * N, T, sizeof(double) * N);
+  const TrajInputRW in(ctx->in.h, N, (int)K);
+  std::memcpy(in.coeffs(), coeffs, sizeof(double) * 18 * N);
+  std::memcpy(in.T(), T, sizeof(double) * N);
+  double *const tk = in.tk();
   {
-    double *tk = ctx->in.h + 19 * N;
     size_t k = 0;
     for (double t = 0.0; t <= dur; t += 0.15) tk[k++] = t;
   }
-  for (size_t i = 0; i < 19 * (size_t)N; ++i)
-    if (!std::isfinite(ctx->in.h[i])) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite trajectory input");
+  for (const double *v = in.coeffs(); v < tk; ++v)   // coeffs and T
+    if (!std::isfinite(*v)) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite trajectory input");
   {
     // Exact cull (k_solve, main points): a point is skipped when  min_c(|p - c_c| - rb_c - slack_c) > safety_hor.
     // Chunk c holds the table times t_k0 .. t_k1; every t of [t_k0 - h, t_k1 + h] lies within h of one of them
@@ -439,11 +426,10 @@ int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bo
     // convex hull of their Bernstein coefficients on the sub-interval.  Then sdf(t) >= |p - x(t)| - R_shape >=
     // |p - c_c| - rb_c - V_c * h for every continuous t, whatever local minimum the reference's search returns,
     // and smoothedL1 (BEO:316-340) is inactive.  Only in the regular regime (traj_duration not stale).
-    const size_t nch = (K + kChunk - 1) / kChunk;
-    double *slack = ctx->in.h + 19 * (size_t)N + K;
-    double *rot = slack + nch;   // W_c * h: yaw-rate allowance of the value-based second cull (scan_layer1)
+    const size_t nch = (size_t)TrajInput::chunk_count((int)K);
+    double *slack = in.slack();
+    double *rot = in.rot();   // W_c * h: yaw-rate allowance of the value-based second cull (scan_layer1)
     ctx->slack_max = 0.0;
-    const double *tk = ctx->in.h + 19 * (size_t)N;
     ctx->cull_ok = (td == dur) && K >= 1;
     std::vector<double> S(N + 1, 0.0);
     for (int i = 0; i < N; ++i) S[i + 1] = S[i] + T[i];
@@ -541,7 +527,7 @@ int build_layer_tables(svsdf_ctx *ctx) {
   const int rows = (mode >= 3) ? svsdf::kLayerRows : 1;
   const size_t lds = (size_t)traj_lds_doubles(ctx->N) * sizeof(double);
   const unsigned grid = (unsigned)((K * (size_t)rows * svsdf::kLayerSteps + 255) / 256);
-  hipLaunchKernelGGL(k_layer_tables, dim3(grid), dim3(256), lds, ctx->stream, ctx->d_traj, ctx->in.d + 19 * (size_t)ctx->N, (int)K, rows, ctx->d_ltab);
+  hipLaunchKernelGGL(k_layer_tables, dim3(grid), dim3(256), lds, ctx->stream, ctx->d_traj, TrajInput(ctx->in.d, ctx->N, ctx->K).tk(), (int)K, rows, ctx->d_ltab);
   if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_LAYER_TABLES, -1, grid, 256, lds, (long long)(K * rows * svsdf::kLayerSteps), 0)) r->targ[0] = mode;
   ctx->ltab_mode = mode;
   return SVSDF_OK;
@@ -684,7 +670,7 @@ int reduce_and_read(svsdf_ctx *ctx, bool with_partial) {
   bool host_written = false;
   if (with_partial) {
     const unsigned grid = (unsigned)std::min<size_t>((ctx->P + kBlock - 1) / kBlock, 512);   // (256 / 1024 / 2048 blocks: within 1 %, round 6)
-    const size_t plen = 19 * (size_t)N + 1;
+    const size_t plen = (size_t)partial_doubles(N);
     if ((size_t)grid * plen > ctx->block_partials_cap) {
       int rc = ctx->d_block_partials.alloc(ctx, (size_t)grid * plen);
       if (rc) return rc;
@@ -740,8 +726,8 @@ int alloc_interior_buffers(svsdf_ctx *ctx, size_t cap);   // below
 int finish(svsdf_ctx *ctx, bool with_partial) {
   int rc = reduce_and_read(ctx, with_partial);
   if (rc) return rc;
-  const unsigned long long *st = reinterpret_cast<const unsigned long long *>(ctx->h_out + kOutPartial);
-  while (st[5] > 0 && ctx->it_done < kMaxIter) {  // solves requested by the last k_round are pending
+  const EvalCounters &cnt = *reinterpret_cast<const EvalCounters *>(ctx->h_out + kOutPartial);
+  while (cnt.pending > 0 && ctx->it_done < kMaxIter) {  // solves requested by the last k_round are pending
     const int it1 = std::min(ctx->it_done + 3, (int)kMaxIter);
     for (int it = ctx->it_done; it < it1; ++it) enqueue_solve_round(ctx, it);
     ctx->it_done = it1;
@@ -749,9 +735,9 @@ int finish(svsdf_ctx *ctx, bool with_partial) {
     HIPCHK(hipMemsetAsync(ctx->d_nonfinite, 0, sizeof(int), ctx->stream));
     if ((rc = reduce_and_read(ctx, with_partial))) return rc;
   }
-  if (st[5] > 0) return fail(ctx, SVSDF_ERR_INVALID, "GSIP iterations exhausted (internal limit)");
+  if (cnt.pending > 0) return fail(ctx, SVSDF_ERR_INVALID, "GSIP iterations exhausted (internal limit)");
   {
-    const size_t n_int = (size_t)st[11 + 2 * kMaxIter];
+    const size_t n_int = (size_t)cnt.n_int;
     if (n_int > ctx->icap) {   // surplus interior points were dropped: grow and repeat (same bits once everything fits)
       rc = alloc_interior_buffers(ctx, std::min(ctx->P, n_int + n_int / 8 + 4096));
       return rc ? rc : kRepeat;
@@ -763,31 +749,31 @@ int finish(svsdf_ctx *ctx, bool with_partial) {
     }
     ctx->icap_fitted = true;
   }
-  ctx->stats.solves = st[0];
-  ctx->stats.sdf_evals = st[1];
-  ctx->stats.scan_evals = st[2];
-  ctx->stats.interior_points = st[3];
-  ctx->stats.gsip_samples = st[6];
-  ctx->stats.gsip_iterations = (unsigned)st[7];
-  ctx->stats.culled_points = st[8];
-  ctx->stats.round_scan_evals = st[9 + kMaxIter];
-  ctx->stats.speculative_evals = st[10 + kMaxIter];
+  ctx->stats.solves = cnt.solves;
+  ctx->stats.sdf_evals = cnt.sdf_evals;
+  ctx->stats.scan_evals = cnt.scan_evals;
+  ctx->stats.interior_points = cnt.interior_points;
+  ctx->stats.gsip_samples = cnt.gsip_samples;
+  ctx->stats.gsip_iterations = (unsigned)cnt.gsip_iterations;
+  ctx->stats.culled_points = cnt.culled_points;
+  ctx->stats.round_scan_evals = cnt.round_scan_evals;
+  ctx->stats.speculative_evals = cnt.speculative_evals;
   ctx->stats.batches = ctx->nbatch;
   {
-    const unsigned long long c = st[12 + 2 * kMaxIter], r = st[13 + 2 * kMaxIter];   // clock probe (BatchCtl::clk)
+    const unsigned long long c = cnt.clk[0], r = cnt.clk[1];   // clock probe (BatchCtl::clk)
     ctx->stats.shader_clock_mhz = r ? (double)c / (double)r * ctx->wall_clock_khz * 1e-3 : 0.0;
   }
-  for (int i = 0; i < kMaxIter; ++i) ctx->prev_nsolve[i] = (long long)st[9 + i];
-  ctx->prev_solves = (long long)st[0];
+  for (int i = 0; i < kMaxIter; ++i) ctx->prev_nsolve[i] = (long long)cnt.n_solve[i];
+  ctx->prev_solves = (long long)cnt.solves;
   ctx->have_prev_nsolve = true;
-  for (int i = 0; i < kMaxIter; ++i) ctx->prev_nactive[i] = (long long)st[11 + kMaxIter + i];
+  for (int i = 0; i < kMaxIter; ++i) ctx->prev_nactive[i] = (long long)cnt.n_active[i];
   ctx->prev_tail_iter = ctx->tail_iter;
   ctx->have_prev_nactive = true;
   ctx->stats.tail_iter = ctx->tail_iter;
-  ctx->stats.tail_points = (ctx->tail_iter >= 0 && ctx->tail_iter < kMaxIter) ? (unsigned long long)st[11 + kMaxIter + ctx->tail_iter] : 0ull;
+  ctx->stats.tail_points = (ctx->tail_iter >= 0 && ctx->tail_iter < kMaxIter) ? cnt.n_active[ctx->tail_iter] : 0ull;
   // next evaluation enqueues as many iterations as this one needed (+1); the slow path above
   // covers an underestimate
-  if (ctx->adaptive_iters && ctx->tail_iter < 0) ctx->first_iters = std::max(2, std::min((int)st[7] + 1, (int)kMaxIter));
+  if (ctx->adaptive_iters && ctx->tail_iter < 0) ctx->first_iters = std::max(2, std::min((int)cnt.gsip_iterations + 1, (int)kMaxIter));
   if (ctx->profile_span && !ctx->profile) {
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, ctx->ev_pool[0], ctx->ev_pool[ctx->e_end]);
@@ -825,7 +811,7 @@ int finish(svsdf_ctx *ctx, bool with_partial) {
     merged(ctx->round_events, ctx->stats.round_ms, ctx->stats.round_ms_sum);
     merged(ctx->tail_events, ctx->stats.tail_ms, ctx->stats.tail_ms_sum);
   }
-  if (st[4]) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite per-point result on the device");
+  if (cnt.nonfinite) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite per-point result on the device");
   return SVSDF_OK;
 }
 
@@ -1008,8 +994,8 @@ int run_pipeline_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double 
 
 void accumulate(int N, const double *partial, double *cost, double *gradT, double *gradC) {
   *cost += partial[0];
-  for (int e = 0; e < 18 * N; ++e) gradC[e] += partial[1 + e];
-  for (int j = 0; j < N; ++j) gradT[j] += partial[1 + 18 * N + j];
+  for (int e = 0; e < 18 * N; ++e) gradC[e] += partial[kPartialGradC + e];
+  for (int j = 0; j < N; ++j) gradT[j] += partial[partial_gradT(N) + j];
 }
 
 // Interior-sized arrays: GSIP state per interior point and the 24 sample slots per interior point (the big ones: 24 x 52 B).
