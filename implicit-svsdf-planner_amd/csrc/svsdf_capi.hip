@@ -193,8 +193,8 @@ svsdf_ctx *svsdf_create(const svsdf_config *cfg) {
     ctx->cfg.polygon_nloops = (int)loops.size();
   }
   ctx->G_env = 0;
-  if (const char *e = std::getenv("SVSDF_G")) { const int g = std::atoi(e); if (g == 1 || g == 2 || g == 4 || g == 8 || g == 16 || g == 32) { ctx->G_env = g; ctx->G = g; ctx->G_late = std::max(g, 8); } }
-  if (const char *e = std::getenv("SVSDF_G_LATE")) { const int g = std::atoi(e); if (g == 1 || g == 2 || g == 4 || g == 8 || g == 16 || g == 32) { ctx->G_late = g; ctx->G_late_env = g; } }
+  if (const char *e = std::getenv("SVSDF_G")) { const int g = std::atoi(e); if (valid_lanes(g)) { ctx->G_env = g; ctx->G = g; ctx->G_late = std::max(g, 8); } }
+  if (const char *e = std::getenv("SVSDF_G_LATE")) { const int g = std::atoi(e); if (valid_lanes(g)) { ctx->G_late = g; ctx->G_late_env = g; } }
   if (const char *e = std::getenv("SVSDF_PRUNE")) ctx->prune = std::atoi(e) != 0;
   if (const char *e = std::getenv("SVSDF_BATCHES")) ctx->want_batches = (std::string(e) == "measure") ? -1 : std::max(0, std::min(std::atoi(e), (int)kMaxBatches));
   if (const char *e = std::getenv("SVSDF_SELECT_DELTA")) { ctx->select_delta = std::atof(e); ctx->select_env = true; }
@@ -212,7 +212,7 @@ svsdf_ctx *svsdf_create(const svsdf_config *cfg) {
   if (const char *e = std::getenv("SVSDF_TAIL_LOCAL")) ctx->tail_local = std::atoi(e) != 0;
   if (const char *e = std::getenv("SVSDF_TAIL_LATENCY")) ctx->tail_latency = std::atoi(e) != 0;
   if (const char *e = std::getenv("SVSDF_TAIL")) ctx->tail_mode = (std::string(e) == "off") ? -2 : (std::string(e) == "auto") ? -1 : std::max(0, std::atoi(e));
-  if (const char *e = std::getenv("SVSDF_UB_FULL")) { ctx->ub_full = std::atoi(e) != 0; ctx->ub_lazy = std::atoi(e) == 2; ctx->ub_anchor = std::atoi(e) == 3; ctx->ub_env = true; }
+  if (const char *e = std::getenv("SVSDF_UB_FULL")) { const int v = std::atoi(e); ctx->bound_mode = (v == 0 || v == 2 || v == 3) ? v : 1; ctx->ub_env = true; }   // (any other value: full scans)
   if (const char *e = std::getenv("SVSDF_PROFILE")) ctx->profile = std::atoi(e) != 0;
   if (const char *e = std::getenv("SVSDF_PIECE_TIME")) {   // exact | fast | auto (default)
     ctx->cfg.flags &= ~(SVSDF_FLAG_EXACT_PIECE_TIME | SVSDF_FLAG_FAST_PIECE_TIME);
@@ -510,7 +510,7 @@ int svsdf_get_plan(const svsdf_ctx *ctx, svsdf_plan *out) {
   out->lanes_per_query = (c->scaled && c->G > 0) ? svsdf::scaled_lanes(c->G) : c->G;
   out->tail_iter = (c->tail_mode == -2 || c->scaled) ? -2 : (c->tail_mode >= 0) ? c->tail_mode : (c->have_prev_nactive ? choose_tail_iter(c) : SVSDF_PLAN_AUTO);
   out->layer_tables = c->layer_tables;
-  out->settled = ((c->ub_env || c->ub_tune > 0) && c->bt_state == 0 && c->an_state == 0 && c->lz_state == 0 && c->have_prev_nsolve) ? 1 : 0;
+  out->settled = plan_settled(c) ? 1 : 0;
   return SVSDF_OK;
 }
 
@@ -518,7 +518,7 @@ int svsdf_set_plan(svsdf_ctx *ctx, const svsdf_plan *plan) {
   if (!ctx || !plan) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_set_plan: null argument");
   const int g = plan->lanes_per_query;
   if (plan->bound_mode < SVSDF_PLAN_AUTO || plan->bound_mode > 3 || plan->batches < -2 || plan->batches == 0 || plan->batches > kMaxBatches ||
-      !(g == SVSDF_PLAN_AUTO || g == 1 || g == 2 || g == 4 || g == 8 || g == 16 || g == 32) || plan->tail_iter < -2 || plan->tail_iter >= kMaxIter ||
+      !(g == SVSDF_PLAN_AUTO || valid_lanes(g)) || plan->tail_iter < -2 || plan->tail_iter >= kMaxIter ||
       !(plan->layer_tables == SVSDF_PLAN_AUTO || plan->layer_tables == 0 || plan->layer_tables == 2 || plan->layer_tables == 3))
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_set_plan: field out of range");
   if (!ctx->subs.empty()) {
@@ -531,11 +531,10 @@ int svsdf_set_plan(svsdf_ctx *ctx, const svsdf_plan *plan) {
   ctx->layer_tables = plan->layer_tables;
   // bound mode: a change invalidates the launch widths on record (they belong to the other mode's solve counts)
   if (plan->bound_mode == SVSDF_PLAN_AUTO) {
-    if (ctx->ub_env) { ctx->ub_env = false; ctx->ub_tune = 0; ctx->have_prev_nsolve = false; ctx->have_prev_nactive = false; }
+    if (ctx->ub_env) { ctx->ub_env = false; ctx->ub_tune = 0; forget_launch_history(ctx); }
   } else {
-    const bool full = plan->bound_mode != 0, lazy = plan->bound_mode == 2, anchor = plan->bound_mode == 3;
-    if (!ctx->ub_env || full != ctx->ub_full || lazy != ctx->ub_lazy || anchor != ctx->ub_anchor) { ctx->have_prev_nsolve = false; ctx->have_prev_nactive = false; ctx->ub_tune = 0; }
-    ctx->ub_env = true; ctx->ub_full = full; ctx->ub_lazy = lazy; ctx->ub_anchor = anchor; ctx->an_state = 0; ctx->lz_state = 0;
+    if (!ctx->ub_env || plan->bound_mode != ctx->bound_mode) { forget_launch_history(ctx); ctx->ub_tune = 0; }   // (the stored mode: pinning 3 again where it runs as 1 is no change)
+    ctx->ub_env = true; ctx->bound_mode = plan->bound_mode; stop_trials(ctx);
   }
   ctx->want_batches = (plan->batches == SVSDF_PLAN_AUTO) ? 0 : (plan->batches == -2) ? -1 : plan->batches;
   ctx->bt_state = 0;

@@ -197,9 +197,6 @@ struct svsdf_ctx {
   // pose tables of scan layers 2 and 3 (k_layer_tables): layer 2's K x 21 poses, layer 3's K x 22 x 21 behind them
   Buf<svsdf::Pose> d_ltab;
   size_t ltab_cap = 0;         // seeds (K) the buffer holds; grown on demand, never per evaluation
-  int layer_tables = -1;       // plan: -1 by the previous evaluation's solve count, 0 off, 2 layer 2 only, 3 layers 2 and 3 (env SVSDF_LAYER_TABLES; same results)
-  int ltab_mode = 0;           // this evaluation: 0 none built, 2 / 3 as above
-  long long prev_solves = 0;   // argmin solves of the previous evaluation (valid with have_prev_nsolve)
   double r_bound = 0.0;    // shape bound radius for the layer-1 chunk pruning (analytic circumradius + offset)
   double r_bound_sampled = 0.0;  // max over a polar grid of |q| - sdf(q): self-check, must not exceed r_bound
   double lipschitz_excess = 0.0; // largest |f(q') - f(q)| - |q' - q| found by the same grid (k_rbound); must be <= 0
@@ -210,57 +207,50 @@ struct svsdf_ctx {
   int N = 0, K = 0;
   int piece_time_mode = 0;     // this trajectory: 0 cumulative form (exactly equivalent here), 1 / 2 faithful chain
   int stats_piece_time = 0;
-
-  // tuning (env SVSDF_G / SVSDF_G_LATE / SVSDF_PRUNE / SVSDF_BLOCK / SVSDF_BATCHES)
-  int G = 0 /* 0 = by shard size */, G_late = 8, prune = 1, block = 64, want_batches = 0, waves_per_cu = 16;
-  bool block_env = false;      // env SVSDF_BLOCK pins the solve kernel's block size (default: by LDS footprint)
-  int late_iter = 4, first_iters = 12, it_done = 0, round_lp8_iters = 3, delta_all_iter = 5;
   int n_cu = 256;
-  int round_blocks_per_cu = 4;   // k_round: blocks per CU the grid is capped at (its blocks fetch further iterations themselves); env SVSDF_ROUND_BPC
   double wall_clock_khz = 100000.0;   // hipDeviceAttributeWallClockRate: rate of the constant counter of the clock probe
-  bool adaptive_iters = true;
-  bool ub_full = false;        // k_round scans every new GSIP sample (seed = tightest layer-1 bound, reused by k_solve)
-  bool ub_lazy = false;        // with ub_full: only the samples in the cheap-bound band are scanned (k_round MODE 2)
-  bool ub_anchor = false;      // with ub_full && !ub_lazy: anchor scans (k_round MODE 3: every third sample, the rest by their Lipschitz bound)
-  int an_state = 0;            // anchor trial: 0 decided / idle, 1 next evaluation counts the full mode's table evaluations, 2 the anchor mode's
-  unsigned long long an_full_evals = 0;
-  int lz_state = 0;            // lazy-scan trial of a small cloud: 0 idle, 1 the next evaluation runs in the lazy mode and is judged by its GSIP solves
-  unsigned long long lz_cheap_solves = 0;
-  bool ub_env = false;         // env SVSDF_UB_FULL=0/1/2 pins the mode, otherwise run_pipeline decides after one evaluation
+
+  // ---- The launch plan: what decides which kernels an evaluation launches and how; every choice gives the same bits.
+  // (Measured constants that nothing sets are constexprs next to their use in svsdf_pipeline.hip, not fields.)
+  // (1) Pinned by the caller: an environment variable read at svsdf_create, or svsdf_set_plan.
+  int prune = 1;               // exact chunk pruning in the layer-1 scans (env SVSDF_PRUNE=0: off; same results)
+  int G_env = 0, G_late_env = 0;   // env SVSDF_G / SVSDF_G_LATE, svsdf_set_plan(lanes_per_query): a pinned width (0: by rule)
+  int want_batches = 0;        // env SVSDF_BATCHES, svsdf_set_plan(batches): > 0 pinned, 0 by rule, -1 measured
+  int round_blocks_per_cu = 4;   // k_round: blocks per CU the grid is capped at (its blocks fetch further iterations themselves); env SVSDF_ROUND_BPC
+  bool ub_env = false;         // env SVSDF_UB_FULL=0/1/2/3 or svsdf_set_plan(bound_mode) pins the bound mode, otherwise run_pipeline_leaf decides after one evaluation
+  int layer_tables = -1;       // -1 by the previous evaluation's solve count, 0 off, 2 layer 2 only, 3 layers 2 and 3 (env SVSDF_LAYER_TABLES; same results)
+  int tail_mode = -1;          // fused GSIP tail (k_tail): -1 by the previous evaluation's active counts, -2 off (launch chain only), >= 0 pinned (env SVSDF_TAIL)
+  bool tail_duo = true;        // k_tail with one point per wave: both half-waves own the point and share its seed scans (env SVSDF_TAIL_DUO=0: off)
+  bool tail_latency = true;    // small launches of k_tail (a wave slot per point at two waves per SIMD) use the instantiation that keeps its ~ 240 VGPRs (env SVSDF_TAIL_LATENCY=0: the 168-VGPR one everywhere; same results)
+  bool tail_local = true;      // k_tail from iteration 0 keeps its points' GSIP state and samples in the wave's LDS (env SVSDF_TAIL_LOCAL=0: global arrays)
+  bool scan_anchors = true;    // seed scans of k_round / k_tail evaluate the anchors of the circle test's survivors first (ChunkAnchor; env SVSDF_SCAN_ANCHORS=0: off; needs lipschitz_ok; same results)
+  bool cull = true, cull2 = true;   // exact culls of provably inactive main points: by the chunk circles; the value-based second one after the table scan (env SVSDF_CULL: 0 neither, 1 the first alone, 2 both)
+  bool select_env = false;     // env SVSDF_SELECT_DELTA set select_delta: it then holds in every bound mode
+  double select_delta = 0.1;   // k_round: solve the samples whose upper bound is within this of the best one first
+  // (2) Decided by rule, from the point set and the first evaluations on it (take_stripe, run_pipeline_leaf).
+  int G = 0 /* 0 = by shard size */, G_late = 8;   // lanes per query of the main solve / of the late GSIP iterations (default_lanes)
+  // GSIP bound mode as stored (the kernels' MODE, svsdf_plan::bound_mode; in force: bound_mode_of): 0 cheap bound, 1 full --
+  // k_round scans every new GSIP sample (seed = tightest layer-1 bound, reused by k_solve) --, 2 lazy -- only the samples in
+  // the cheap-bound band are scanned --, 3 anchor -- every third sample scanned, the rest by their Lipschitz bound
+  int bound_mode = 0;
   int ub_tune = 0;             // evaluations since the point set changed that took part in the decision (0 or 1)
   double ub_ratio = 0.0;       // GSIP solves / GSIP samples of the deciding (cheap-bound) evaluation
-  double ub_threshold = 0.5;   // env SVSDF_UB_RATIO (analytic shapes; Polygon 0.2)
-  bool ub_thr_env = false;
-  bool scan_anchors = true;    // seed scans of k_round / k_tail evaluate the anchors of the circle test's survivors first (ChunkAnchor; env SVSDF_SCAN_ANCHORS=0: off; needs lipschitz_ok; same results)
-  int round_list = 3;          // k_round: per-point candidate-chunk lists (env SVSDF_ROUND_LIST: bit 0 scans, bit 1 cheap bound use them; 0: all chunks; same results)
-  bool cull = true;            // exact cull of provably inactive points in the main solve (env SVSDF_CULL=0 disables)
-  bool cull_ok = false;        // this trajectory: duration not stale, slack table valid
-  bool cull2 = true;           // second, value-based exact cull after the table scan (env SVSDF_CULL=1 turns only this one off)
-  double slack_max = 0.0;      // max over the chunks of the linear continuous-path allowance
-  int G_env = 0, G_late_env = 0;
+  int an_state = 0;            // anchor trial: 0 decided / idle, 1 next evaluation counts the full mode's table evaluations, 2 the anchor mode's
+  int lz_state = 0;            // lazy-scan trial of a small cloud: 0 idle, 1 the next evaluation runs in the lazy mode and is judged by its GSIP solves
+  unsigned long long an_full_evals = 0, lz_cheap_solves = 0;   // what each trial compares against
   // batch count of a large shard in the scanning bound modes: chosen by timing real evaluations (any split gives the
   // same bits): 0 idle / done, 1 next evaluation learns the launch plan with one batch, 2.. timing candidate bt_k
   int bt_state = 0, bt_k = 0, bt_rep = 0, bt_ncand = 0, bt_cand[3] = {1, 1, 1};
   double bt_ms[3] = {0, 0, 0}, bt_samples[3] = {0, 0, 0};
-  long long prev_nsolve[svsdf::kMaxIter] = {};  // solves per GSIP iteration of the previous evaluation (same point set)
-  bool have_prev_nsolve = false;
-  // fused GSIP tail (k_tail): all iterations from tail_iter on in one launch per batch
-  int tail_mode = -1;                    // -1: by the previous evaluation's active counts, -2: off (launch chain only), >= 0: pinned
-  long long tail_below = 0;              // auto: the whole GSIP loop runs in k_tail when the shard has at most this many interior
-                                         // points; 0 = what one generation of waves holds (24 per CU: 6144 on 256 CUs)
-  int tail_all_after = 1 << 30;          // steps of a point inside k_tail after which every sample is requested (-1: like the chain)
-  int tail_iter = -1;                    // this evaluation: iteration the tail starts at (-1: none)
-  bool tail_duo = true;                  // k_tail with one point per wave: both half-waves own the point and share its seed scans (env SVSDF_TAIL_DUO=0: off)
-  bool tail_latency = true;              // small launches of k_tail (a wave slot per point at two waves per SIMD) use the instantiation that keeps its ~ 240 VGPRs (env SVSDF_TAIL_LATENCY=0: the 168-VGPR one everywhere; same results)
-  bool tail_local = true;                // k_tail from iteration 0 keeps its points' GSIP state and samples in the wave's LDS (env SVSDF_TAIL_LOCAL=0: global arrays)
-  long long prev_nactive[svsdf::kMaxIter] = {}; // active GSIP points per iteration of the previous evaluation, up to its tail
-  int prev_tail_iter = -1;
-  bool have_prev_nactive = false;
-  long long wide32_below = 2000, wide16_below = 5000, wide8_below = 40000;  // env SVSDF_WIDE32 / SVSDF_WIDE16 / SVSDF_WIDE8
-  bool select_env = false, all_iter_env = false;
-  double scan_delta = 0.002;   // the same band in the scanning bound modes, where the bound is the sample's own table minimum (round 6 sweep, 0 ... 0.01:
-                               // sdHeart / anchor mode - 3.5 % at 0.001 - 0.002 m -- 7 % fewer solves --, C3 / NS / C5 / C2 within +- 0.5 %; 0.01 m until round 5)
-  double select_delta = 0.1;  // k_round: solve the samples whose upper bound is within this of the best one first
+  // (3) Learned from the previous evaluation of this point set (finish).  first_iters alone survives a new point set.
+  int first_iters = 12, it_done = 0;   // iterations the launch chain enqueues up front (the previous evaluation's count + 1) / enqueued so far in this evaluation
+  long long prev_nsolve[svsdf::kMaxIter] = {}, prev_solves = 0;   // solves per GSIP iteration / in all (valid with have_prev_nsolve)
+  long long prev_nactive[svsdf::kMaxIter] = {}; // active GSIP points per iteration, up to its tail
+  int prev_tail_iter = -1;     // iteration the previous evaluation's tail started at
+  bool have_prev_nsolve = false, have_prev_nactive = false;
+  int ltab_mode = 0, tail_iter = -1;   // this evaluation, what the plan came to: layer tables built (0 none, 2 / 3 as layer_tables); iteration the fused tail starts at (-1: none)
+  bool cull_ok = false;        // this trajectory: duration not stale, slack table valid
+  double slack_max = 0.0;      // max over the chunks of the linear continuous-path allowance
   // time-varying robot scale (svsdf_set_scale): the scaled kernels, launch chain only, no culls, every GSIP
   // sample requested
   bool scaled = false;
@@ -285,7 +275,6 @@ struct svsdf_ctx {
   double *h_out_dev = nullptr;    // the same buffer as the device addresses it (k_reduce writes the result there); null: copy
   Buf<unsigned> d_ticket;         // k_reduce: finished-block counter (zero between launches)
   Buf<int> d_nonfinite;
-  int h_nonfinite = 0;
   size_t e_end = 0;
 
   // front-end batches (row f3): growing staging [father | child | pts | kt] + offsets (doubles), and the flags
@@ -361,11 +350,30 @@ constexpr int kRepeat = -12345;   // finish(): more interior points than capacit
 
 extern const char *kShapeNames[SVSDF_SHAPE_COUNT];
 
+// ---- The plan's helpers.  The bound mode in force: the stored one, except that the anchor mode needs a 1-Lipschitz shape SDF and runs as the full
+// mode without one (the only place that demotes).  In force (this function) is what svsdf_get_plan, fill_mode_stats
+// (svsdf_stats::gsip_bound_mode), launch_round and launch_tail see; stored (ctx->bound_mode) what enqueue_solve_round's seed
+// hand-off (any scanning mode: != 0), run_pipeline_leaf's decision and trials and svsdf_set_plan's change test see.
+inline int bound_mode_of(const svsdf_ctx *c) { return (c->bound_mode == 3 && !c->lipschitz_ok) ? 1 : c->bound_mode; }
+// Forgetting what the previous evaluation taught: the solve counts (launch widths, layer tables) alone, or with them the active counts (fused tail)
+inline void forget_solve_counts(svsdf_ctx *c) { c->have_prev_nsolve = false; }
+inline void forget_launch_history(svsdf_ctx *c) { c->have_prev_nsolve = false; c->have_prev_nactive = false; }
+inline void stop_trials(svsdf_ctx *c) { c->an_state = 0; c->lz_state = 0; }
+// A new point set: nothing learned or decided on the old one holds (a pinned bound mode stays; so does first_iters).
+inline void reset_plan(svsdf_ctx *c) {
+  forget_launch_history(c); stop_trials(c);
+  c->prev_tail_iter = -1; c->ub_tune = 0; c->bt_state = 0; c->ub_ratio = 0.0;
+  if (!c->ub_env) c->bound_mode = 0;
+}
+// nothing left to decide, try or measure, and the launch widths are on record (svsdf_plan::settled, svsdf_stats::plan_settled)
+inline bool plan_settled(const svsdf_ctx *c) { return (c->ub_env || c->ub_tune > 0) && !c->bt_state && !c->an_state && !c->lz_state && c->have_prev_nsolve; }
+inline bool valid_lanes(int g) { return g == 1 || g == 2 || g == 4 || g == 8 || g == 16 || g == 32; }
+// Interior points up to which the fused tail owns the whole GSIP loop and a cheap-bound cloud tries the lazy mode: one generation of waves (6144 on 256 CUs)
+inline long long tail_interior_limit(const svsdf_ctx *c) { return (long long)c->n_cu * 24; }
 // Lanes per query of the main solve by shard size: small shards are latency chains (wide groups shorten them), large ones
 // throughput (narrow groups waste fewer lanes; the descent's ladders share the wave anyway).  Crossovers re-measured in
 // round 4 after the shared ladders (profiles/r04_lanes_sweep.txt: 100 k points 8 -> 4 lanes - 5 %, 200 k 8 -> 2 lanes - 7 %).
 // (Polygon: never below 4 -- its 2-lane kernel spills under the 3-waves register cap.)
-inline int bound_mode_of(const svsdf_ctx *c) { return c->ub_full ? (c->ub_lazy ? 2 : ((c->ub_anchor && c->lipschitz_ok) ? 3 : 1)) : 0; }
 inline int default_lanes(const svsdf_ctx *ctx, size_t Ps) {
   const int g = (Ps < 3000) ? 32 : (Ps < 20000) ? 16 : (Ps < 75000) ? 8 : (Ps < 150000) ? 4 : 2;
   return (ctx->cfg.shape_id == (int)svsdf::kPolygon) ? std::max(g, 4) : g;

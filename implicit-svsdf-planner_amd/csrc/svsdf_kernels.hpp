@@ -182,6 +182,18 @@ static_assert(sizeof(EvalCounters) == (14 + 2 * kMaxIter) * 8 && offsetof(EvalCo
               offsetof(EvalCounters, round_scan_evals) == (9 + kMaxIter) * 8 && offsetof(EvalCounters, n_active) == (11 + kMaxIter) * 8 &&
               offsetof(EvalCounters, n_int) == (11 + 2 * kMaxIter) * 8 && offsetof(EvalCounters, clk) == (12 + 2 * kMaxIter) * 8,
               "EvalCounters: the counters row keeps its bytes");
+// ---- Flag words that host and kernels share, each bit defined once (plain constants: the kernels test them inline) ----
+// `prune` of k_solve (SolveLaunch::prune); k_tail's `prune` carries kSolvePrune alone:
+constexpr int kSolvePrune = 1;      // exact chunk pruning in the layer-1 scan
+constexpr int kSolveSolo = 2;       // one query per wave (the launch is sized for it): the descents take the fused pass
+constexpr int kSolveLayer2 = 4;     // the launch carries the pose table of scan layer 2 (SolveLaunch::ltab)
+constexpr int kSolveLayer3 = 8;     // ... and layer 3's behind it
+// `clist_on` of k_round and k_tail; the k_tail bits are zero in a k_round launch, and a round builds the point's list whenever the word is not zero:
+constexpr int kListScans = 1;       // seed scans walk the per-point candidate-chunk list (clear: all chunks; same results)
+constexpr int kListCheap = 2;       // the cheap bound walks it too
+constexpr int kTailLocalState = 4;  // k_tail from iteration 0: the points' GSIP state and samples live in the wave's LDS
+constexpr int kTailNoDuo = 8;       // SET turns the duo OFF (k_tail, one point per wave: both half-waves own the point); clear: on
+constexpr int kScanAnchors = 16;    // seed scans evaluate the anchors of the circle test's survivors first (ChunkAnchor)
 
 // lds must hold 20N+1 doubles: T[N] | S[N+1] | c[18N]
 __device__ __forceinline__ TrajL stage_traj(const TrajDev *__restrict__ g, double *lds) {
@@ -1588,14 +1600,14 @@ template <int SHAPE, int G, int U, typename... Scl>
 __global__ void __launch_bounds__(kBlock, is_polygon<SHAPE>() ? 3 : SVSDF_SOLVE_WAVES)
 k_solve(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Pose *__restrict__ pose_g,
         const Chunk *__restrict__ chunks_g, ShapeParams sp, QuerySet qs, double *__restrict__ out_sdf,
-        double *__restrict__ out_t, int prune /* bit 0: exact chunk pruning; bit 1: one query per wave; bits 2, 3: layer tables */, BatchCtl *__restrict__ ctl, int work_idx, double cull_thresh,
+        double *__restrict__ out_t, int prune /* kSolvePrune | kSolveSolo | kSolveLayer2 | kSolveLayer3 */, BatchCtl *__restrict__ ctl, int work_idx, double cull_thresh,
         const double *__restrict__ rot, double slack_max, Scl... scl_arg, const Pose *__restrict__ ltab_g /* layer pose tables or null */) {
   constexpr bool SC = ScaleArg<Scl...>::SC;
   const ScaleDev scl = ScaleArg<Scl...>::get(scl_arg...);
   extern __shared__ double solve_lds[];
   int n;
   const long long total = qs_total(qs, n);
-  if (total <= 0 || (long long)blockIdx.x * (((prune & 2) != 0) ? (blockDim.x >> 6) : (blockDim.x / G)) >= total) return;
+  if (total <= 0 || (long long)blockIdx.x * (((prune & kSolveSolo) != 0) ? (blockDim.x >> 6) : (blockDim.x / G)) >= total) return;
   const int K = trg->K;
   const int nch = (K + kChunk - 1) / kChunk;   // (TrajInput::chunk_count written out: the call moved this kernel's register allocation)
   stage_poly_edges<SHAPE>(sp, solve_lds);
@@ -1622,18 +1634,18 @@ k_solve(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Po
   // Work distribution: a wave's FIRST 64 / G queries are its own (wave index: no atomic), the following ones come from
   // the launch's cursor.  (All waves of a launch start together: with a fetch first, their 3000 atomics on one address
   // take ~ 12 ns each, one after the other -- the last wave would start ~ 37 us late, in every launch of the chain.)
-  // `prune` bit 1 (round 6; launches of a few hundred queries, i.e. the main solve at the reference's own scale): ONE query per
+  // kSolveSolo (round 6; launches of a few hundred queries, i.e. the main solve at the reference's own scale): ONE query per
   // wave -- the other lane groups stay empty -- so that every descent is "the wave's last open one" from its first pass on and
   // takes the fused pass (derivative + both signs of the ladder in one step: descend_from_seed) instead of two dependent
   // steps per pass.  The chip has a wave slot for every query there; the launch is a chain of dependent evaluations.
-  const bool solo = (prune & 2) != 0;
-  // `prune` bits 2 / 3: the launch carries the pose table of scan layer 2 / of layer 3 behind it (LayerTab, read by this wave only)
+  const bool solo = (prune & kSolveSolo) != 0;
+  // kSolveLayer2 / kSolveLayer3: the launch carries the pose table of scan layer 2 / of layer 3 behind it (LayerTab, read by this wave only)
   if ((threadIdx.x & 63) == 0) {
     LayerTab *lt = wave_layer_tab<G>(wave_lds);
-    lt->l2 = (prune & 4) ? ltab_g : nullptr;
-    lt->l3 = (prune & 8) ? ltab_g + (size_t)K * kLayerSteps : nullptr;
+    lt->l2 = (prune & kSolveLayer2) ? ltab_g : nullptr;
+    lt->l3 = (prune & kSolveLayer3) ? ltab_g + (size_t)K * kLayerSteps : nullptr;
   }
-  prune &= 1;
+  prune &= kSolvePrune;
   const long long per_wave = solo ? 1 : 64 / G;
   const long long n_static = (long long)gridDim.x * (blockDim.x >> 6) * per_wave;
   for (int guard = 0; guard < (1 << 26); ++guard) {
@@ -2139,7 +2151,7 @@ __device__ __forceinline__ void round_point(const ShapeParams &sp, const Pose *p
             // cheap upper bound: best table pose of the chunk with the nearest centre (any chunk is valid)
             double d2min = 1e300;
             int c0 = 0;
-            const int ncl_c = (clist_on & 2) ? ncl : -1;
+            const int ncl_c = (clist_on & kListCheap) ? ncl : -1;
             const int nl_c = (ncl_c < 0) ? nch : ncl_c;
             for (int jc = 0; jc < nl_c; ++jc) {
               const int c = (ncl_c < 0) ? jc : (int)clist[jc];
@@ -2226,7 +2238,7 @@ __device__ __forceinline__ void round_point(const ShapeParams &sp, const Pose *p
             int bk = 0;
             if (found) {
               bool cu;
-              scan_layer1<SHAPE, 8, true>(sp, pose, chunks, K, nch, qx, qy, 1, __longlong_as_double(0x7ff0000000000000ll), bd, bk, cu, n_scan, clist, (clist_on & 1) ? ncl : -1, rc + 8, nullptr, 0.0, anch);
+              scan_layer1<SHAPE, 8, true>(sp, pose, chunks, K, nch, qx, qy, 1, __longlong_as_double(0x7ff0000000000000ll), bd, bk, cu, n_scan, clist, (clist_on & kListScans) ? ncl : -1, rc + 8, nullptr, 0.0, anch);
             }
 #pragma unroll
             for (int ps = 0; ps < NP; ++ps) {
@@ -2301,7 +2313,7 @@ __device__ __forceinline__ void round_point(const ShapeParams &sp, const Pose *p
           int bk = 0;
           if (sidx < n_emit) {
             bool cu;
-            scan_layer1<SHAPE, 8, true>(sp, pose, chunks, K, nch, qx, qy, 1, __longlong_as_double(0x7ff0000000000000ll), bd, bk, cu, n_scan, clist, (clist_on & 1) ? ncl : -1, rc + 8, nullptr, 0.0, anch);
+            scan_layer1<SHAPE, 8, true>(sp, pose, chunks, K, nch, qx, qy, 1, __longlong_as_double(0x7ff0000000000000ll), bd, bk, cu, n_scan, clist, (clist_on & kListScans) ? ncl : -1, rc + 8, nullptr, 0.0, anch);
           }
           // hand the result to the lane that owns the sample: sub-group (j % SG) scanned sample j in pass j / SG
           const double rb = __shfl(bd, (l % SG) * 8, LP);
@@ -2390,7 +2402,7 @@ __device__ __forceinline__ void round_point(const ShapeParams &sp, const Pose *p
             int bk = 0;
             if (found) {
               bool cu;
-              scan_layer1<SHAPE, 8, true>(sp, pose, chunks, K, nch, qx, qy, 1, __longlong_as_double(0x7ff0000000000000ll), bd, bk, cu, n_scan, clist, (clist_on & 1) ? ncl : -1, rc + 8, nullptr, 0.0, anch);
+              scan_layer1<SHAPE, 8, true>(sp, pose, chunks, K, nch, qx, qy, 1, __longlong_as_double(0x7ff0000000000000ll), bd, bk, cu, n_scan, clist, (clist_on & kListScans) ? ncl : -1, rc + 8, nullptr, 0.0, anch);
             }
 #pragma unroll
             for (int ps = 0; ps < NP; ++ps) {
@@ -2562,7 +2574,7 @@ k_round(const TrajDev *__restrict__ trg, const Pose *__restrict__ pose_g,
       a = cur[e];
       round_point<SHAPE, LP, MODE>(sp, pose, chunks, K, nch, px_, py_, gs, stride, start, a, delta, band_delta, res_sdf,
                                    res_t, res_gx, res_gy, n_scan, ro, s_clist + (size_t)hw * kMaxCand, clist_on, rc, -1,
-                                   (clist_on & 16) ? reinterpret_cast<const ChunkAnchor *>(chunks_g + nch) : nullptr);
+                                   (clist_on & kScanAnchors) ? reinterpret_cast<const ChunkAnchor *>(chunks_g + nch) : nullptr);
     }
     if (l == 0) {
       const int ent = nbuf * PPB + hw;
@@ -2754,7 +2766,7 @@ k_tail(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Pos
   }
   const TrajL tr = stage_traj(trg, tab_lds + 4 * (size_t)K + 4 * (size_t)nch);  // ends with __syncthreads (the only block barrier)
   const size_t tables = poly_lds_doubles<SHAPE>(sp.nverts) + 4 * (size_t)K + 4 * (size_t)nch + (size_t)traj_lds_doubles(tr.N);   // = block_table_doubles
-  const bool local = it0 == 0 && (clist_on & 4) != 0;   // (bit 2 of clist_on: the host's switch, SVSDF_TAIL_LOCAL=0 turns it off; see below)
+  const bool local = it0 == 0 && (clist_on & kTailLocalState) != 0;   // (the host's switch, SVSDF_TAIL_LOCAL=0 turns it off; see below)
   // per-wave stride: the wave-local GSIP block (the last part of a wave's region) only exists when it is used (launch_tail
   // sizes the launch's LDS the same way)
   const size_t wave_stride = local ? kTailWaveLds : kTailWaveLds - kTailLocalBytes;
@@ -2785,7 +2797,7 @@ k_tail(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Pos
   // One point per wave (ppw == 1: the launch is a latency chain and has a wave for every point): both half-waves OWN that
   // point -- same state, same decisions, same stores -- and share its seed scans (round_point's `duo`); only half 0's
   // requests go to the wave's solve list.  (The scanning bound modes; the cheap mode has no scans to share.)
-  const bool duo = ppw == 1 && MODE != 0 && (clist_on & 8) == 0;
+  const bool duo = ppw == 1 && MODE != 0 && (clist_on & kTailNoDuo) == 0;
   const int hs = duo ? 0 : h;   // the half whose slot of the wave-local GSIP state this lane uses
   const unsigned lt_mask = (1u << l) - 1u;
   unsigned n_eval = 0, n_scan = 0, n_solved = 0, n_spec = 0, n_rscan = 0;
@@ -2841,7 +2853,7 @@ k_tail(const TrajDev *__restrict__ trg, const double *__restrict__ tk, const Pos
       const double dl = (steps >= all_after) ? 1e300 : delta, bd = (steps >= all_after) ? 1e300 : band_delta;
       round_point<SHAPE, LP, MODE, true>(sp, pose, chunks, K, nch, px_, py_, ga, stride_a, start, local ? hs : a, dl, bd, res_sdf, res_t, res_gx,
                                    res_gy, n_rscan, ro, clist_w + (size_t)h * kMaxCand, clist_on, rc, duo ? h : -1,
-                                   (clist_on & 16) ? reinterpret_cast<const ChunkAnchor *>(chunks_g + nch) : nullptr);
+                                   (clist_on & kScanAnchors) ? reinterpret_cast<const ChunkAnchor *>(chunks_g + nch) : nullptr);
       ++steps;
       if (ro.n_emit > 0) own = true;
       if (l == 0 && (!duo || h == 0)) n_emit_tot += ro.n_emit;

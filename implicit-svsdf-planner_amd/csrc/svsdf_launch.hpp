@@ -15,20 +15,20 @@ constexpr int kNSlices = 4;
 
 struct SolveLaunch {   // arguments of k_solve<SHAPE, G, 1>
   const TrajDev *traj; const double *tk; const Pose *pose; const Chunk *chunks; ShapeParams sp; QuerySet qs;
-  double *out_sdf, *out_t; int prune; BatchCtl *ctl; int work_idx; double cull_thresh;
+  double *out_sdf, *out_t; int prune /* kSolve* bits */; BatchCtl *ctl; int work_idx; double cull_thresh;
   const double *rot; double slack_max;   // second exact cull (main points): per-chunk yaw allowance W_c h, max_c of the linear one
   const ScaleDev *scl = nullptr;         // not null: k_solve<SHAPE, G, 1, ScaleDev> under this scale schedule (G in kScaledLanes)
-  const Pose *ltab = nullptr;            // layer-2 pose table, layer 3's behind it (k_layer_tables); `prune` bits 2 / 3 say which the launch uses
+  const Pose *ltab = nullptr;            // layer-2 pose table, layer 3's behind it (k_layer_tables); kSolveLayer2 / kSolveLayer3 in `prune` say which the launch uses
 };
 struct RoundLaunch {   // arguments of k_round<SHAPE, LP, MODE>
   const TrajDev *traj; const Pose *pose; const Chunk *chunks; ShapeParams sp; const double *px, *py; GsipState gs;
   size_t stride; int it; double delta, band_delta; double *res_sdf, *res_t, *res_gx, *res_gy; BatchCtl *ctl;
-  int clist_on;   // 1: scans / cheap bounds walk the per-point candidate-chunk list (0: all chunks; same results)
+  int clist_on;   // kListScans | kListCheap | kScanAnchors (svsdf_kernels.hpp)
 };
 struct TailLaunch {    // arguments of k_tail<SHAPE, MODE, WAVES>
   const TrajDev *traj; const double *tk; const Pose *pose; const Chunk *chunks; ShapeParams sp; const double *px, *py;
   GsipState gs; size_t stride; int it0, prev_mode; double delta, band_delta; int all_after, ppw;
-  double *res_sdf, *res_t, *res_gx, *res_gy; BatchCtl *ctl; int clist_on, prune;
+  double *res_sdf, *res_t, *res_gx, *res_gy; BatchCtl *ctl; int clist_on, prune;   // clist_on: k_round's bits | kTailLocalState | kTailNoDuo; prune: kSolvePrune
   int latency;   // not a kernel argument: 1 = the instantiation that keeps its registers (kTailLatencyWaves per SIMD, no scratch)
 };
 struct ClassifyLaunch {   // arguments of k_classify<SHAPE>

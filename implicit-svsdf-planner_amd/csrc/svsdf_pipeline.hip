@@ -200,12 +200,14 @@ static void lds_too_long(svsdf_ctx *ctx, const std::string &what) {
   if (ctx->launch_err.empty()) ctx->launch_err = "trajectory too long for the LDS pose table (" + what + ")";
 }
 // GSIP selection of k_round / k_tail: band `sel` below the best bound, every sample from iteration `all_it` on.
-// The seed bound of the scanning modes is tight: a narrow band selects (ctx->scan_delta: 0.002 m, solve-all from
-// iteration 7); the chunk bound of the cheap mode needs 0.1 m / iteration 5.  SVSDF_SELECT_DELTA overrides both.
+// The seed bound of the scanning modes is the sample's own table minimum and tight: a narrow band selects (kScanDelta,
+// solve-all from iteration 7); the cheap mode's chunk bound needs 0.1 m / iteration 5.  SVSDF_SELECT_DELTA sets every mode's band.
 struct GsipSelect { double sel; int all_it; };
 static GsipSelect gsip_select(const svsdf_ctx *ctx, int mode) {
+  // round 6 sweep, 0 ... 0.01: sdHeart / anchor mode - 3.5 % at 0.001 - 0.002 m -- 7 % fewer solves --, C3 / NS / C5 / C2 within +- 0.5 %; 0.01 m until round 5
+  constexpr double kScanDelta = 0.002; constexpr int kAllIterCheap = 5, kAllIterScans = 7;
   const bool scans = mode != 0;
-  return {(scans && !ctx->select_env) ? ctx->scan_delta : ctx->select_delta, (scans && !ctx->all_iter_env) ? 7 : ctx->delta_all_iter};
+  return {(scans && !ctx->select_env) ? kScanDelta : ctx->select_delta, scans ? kAllIterScans : kAllIterCheap};
 }
 
 // Dynamic LDS of one block (svsdf::block_table_doubles): the tables -- a Polygon's edges in front of them while the block
@@ -220,9 +222,8 @@ static BlockLds plan_block_lds(const svsdf_ctx *ctx, TableUser user, size_t per_
   for (r.poly_lds = poly_lds;; r.poly_lds = false) {
     const size_t lds = block_table_doubles(ctx->K, ctx->N, r.poly_lds ? (size_t)svsdf::kPolyEdgeDoubles * (size_t)ctx->sp.nverts : 0,
                                            user != TableUser::Round) * sizeof(double);
-    r.block = (user == TableUser::Solve) ? ctx->block : (user == TableUser::Tail) ? kTailBlock : kRoundBlock;
-    if (user == TableUser::Solve && !ctx->block_env)
-      r.block = ((lds + per_wave) * 12 <= 160 * 1024) ? 64 : ((lds + 2 * per_wave) * 6 <= 160 * 1024) ? 128 : 256;
+    r.block = (user == TableUser::Solve) ? (((lds + per_wave) * 12 <= 160 * 1024) ? 64 : ((lds + 2 * per_wave) * 6 <= 160 * 1024) ? 128 : 256)
+              : (user == TableUser::Tail) ? kTailBlock : kRoundBlock;
     r.bytes = (user == TableUser::Round) ? lds : ((lds + 15) & ~(size_t)15) + (size_t)(r.block / 64) * per_wave;
     r.fits = r.bytes + (user == TableUser::Round ? 16384 : 0) <= ctx->lds_limit;
     if (r.fits || !r.poly_lds || !fall_back) return r;
@@ -243,7 +244,7 @@ void launch_solve(svsdf_ctx *ctx, int G, hipStream_t st, const QuerySet &qs, lon
     cull_thresh = std::numeric_limits<double>::infinity();
   }
   // a launch of at most one query per SIMD with 32-lane groups (the main solve of a reference-scale cloud): one query per
-  // wave, so that the descents take the fused pass (k_solve, `prune` bit 1)
+  // wave, so that the descents take the fused pass (k_solve, kSolveSolo)
   const bool solo = G == 32 && !ctx->G_env && max_queries <= (long long)ctx->n_cu * 4;
   const long long lanes = std::max<long long>(max_queries * (solo ? 64 : G), 64);
   // Every block stages the pose table + chunk bounds + trajectory into LDS (13 KB at 16 pieces x 2.5 s, 24 KB at 32):
@@ -255,10 +256,11 @@ void launch_solve(svsdf_ctx *ctx, int G, hipStream_t st, const QuerySet &qs, lon
   const BlockLds l = plan_block_lds(ctx, TableUser::Solve, wlds, ctx->poly_lds);
   const int blk = l.block;
   if (!l.fits) return lds_too_long(ctx, std::to_string(l.bytes) + " B of " + std::to_string(ctx->lds_limit) + " B per block");
-  const unsigned grid = (unsigned)std::min<long long>((lanes + blk - 1) / blk, (long long)(256 * ctx->waves_per_cu * 64) / blk);
+  constexpr int kSolveGridWaves = 256 * 16;   // the persistent grid's cap: 16 waves for each of 256 CUs
+  const unsigned grid = (unsigned)std::min<long long>((lanes + blk - 1) / blk, (long long)(kSolveGridWaves * 64) / blk);
   // (the second, value-based cull runs with the first one: main points of an evaluation that may cull)
   const bool cull2 = std::isfinite(cull_thresh) && ctx->cull2;
-  const SolveLaunch a{ctx->d_traj, in.tk(), ctx->d_pose, ctx->d_chunks, ctx->sp, qs, out_sdf, out_t, ctx->prune | (solo ? 2 : 0) | (ctx->ltab_mode >= 2 ? 4 : 0) | (ctx->ltab_mode >= 3 ? 8 : 0), ctl, work_idx, cull_thresh,
+  const SolveLaunch a{ctx->d_traj, in.tk(), ctx->d_pose, ctx->d_chunks, ctx->sp, qs, out_sdf, out_t, (ctx->prune ? kSolvePrune : 0) | (solo ? kSolveSolo : 0) | (ctx->ltab_mode >= 2 ? kSolveLayer2 : 0) | (ctx->ltab_mode >= 3 ? kSolveLayer3 : 0), ctl, work_idx, cull_thresh,
                       cull2 ? in.rot() : nullptr, ctx->slack_max, ctx->scaled ? &ctx->scale : nullptr, ctx->d_ltab};
   const int shape = l.poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
   {
@@ -288,18 +290,19 @@ void launch_round(svsdf_ctx *ctx, hipStream_t st, int b, int it) {
   // iterations 0 and 1 are (almost always) GSIP rounds 1 and 2 with 2 and 6 samples: 8 lanes per point; later rounds have
   // 18-21 samples: 32 lanes per point (either handles any count).  Iteration 2 (18 samples, still every interior point
   // active: throughput, not latency) also runs faster with 8 lanes and three sample passes per point -- measured round 3,
-  // SVSDF_ROUND_LP8_ITERS 2 / 3 / 4 / 6 / all: C3 6.15 / 5.97 / 6.12 / 6.33 / 6.45 ms, NS 7.49 / 7.24 / 7.21 / 7.31 / 7.58
+  // 8 lanes in the first 2 / 3 / 4 / 6 / all iterations: C3 6.15 / 5.97 / 6.12 / 6.33 / 6.45 ms, NS 7.49 / 7.24 / 7.21 / 7.31 / 7.58
   // (round 6, re-measured with the balanced launches: 2 / 3 / 4 / 6 iterations -- C3 5.80 / 5.63 / 5.67 / 5.87 ms, C4 6.26 / 5.84 /
   // 5.88 / 6.00; the lazy mode, whose launches scan few samples per point, gains from a fourth: NS 7.45 / 7.17 / 7.03 / 7.05)
-  const int lp = (it < ctx->round_lp8_iters + (mode == 2 ? 1 : 0)) ? 8 : 32;
+  constexpr int kRoundLp8Iters = 3;
+  const int lp = (it < kRoundLp8Iters + (mode == 2 ? 1 : 0)) ? 8 : 32;
   const unsigned grid = (unsigned)std::min<long long>((pts * lp + kRoundBlock - 1) / kRoundBlock, (long long)ctx->n_cu * ctx->round_blocks_per_cu);
   const RoundLaunch a{ctx->d_traj, ctx->d_pose, ctx->d_chunks, ctx->sp, ctx->d_px, ctx->d_py, ctx->gs, ctx->icap, it, delta,
-                      band_delta, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy, ctx->d_ctl + b, ctx->round_list | ((ctx->scan_anchors && ctx->lipschitz_ok) ? 16 : 0)};
+                      band_delta, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy, ctx->d_ctl + b, kListScans | kListCheap | ((ctx->scan_anchors && ctx->lipschitz_ok) ? kScanAnchors : 0)};
   const int shape = l.poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
   const ProfileSpan span(ctx, st, ctx->round_events);
   launch_result(ctx, launch_k_round(shape, lp, mode, grid, l.bytes, st, a), "k_round");
   if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_ROUND, compiled_shape(shape), grid, (unsigned)kRoundBlock, l.bytes, pts, b)) {
-    r->targ[0] = lp; r->targ[1] = mode; r->iter = it; r->anchors = (a.clist_on & 16) ? 1 : 0;
+    r->targ[0] = lp; r->targ[1] = mode; r->iter = it; r->anchors = (a.clist_on & kScanAnchors) ? 1 : 0;
   }
   debug_sync(st, "k_round", lp * 10 + mode, it);
 }
@@ -308,7 +311,7 @@ void launch_round(svsdf_ctx *ctx, hipStream_t st, int b, int it) {
 void launch_tail(svsdf_ctx *ctx, hipStream_t st, int b, int it0) {
   const int mode = bound_mode_of(ctx);
   const GsipSelect gsel = gsip_select(ctx, mode);
-  const int all_after = (ctx->tail_all_after < 0) ? std::max(0, gsel.all_it - it0) : ctx->tail_all_after;
+  constexpr int kTailAllAfter = 1 << 30;   // steps of a point inside k_tail after which every sample is requested: never
   // the active count lives on the device; the grid is sized by what the previous evaluation had there (surplus blocks
   // exit at once, missing ones are made up for by the waves' work fetch)
   long long pts = std::max(1, ctx->bcount[b]);
@@ -328,8 +331,8 @@ void launch_tail(svsdf_ctx *ctx, hipStream_t st, int b, int it0) {
   const long long per_block = (kTailBlock / 64) * ppw;
   const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>((pts + per_block - 1) / per_block, (long long)ctx->n_cu * 3));
   const TailLaunch a{ctx->d_traj, TrajInput(ctx->in.d, ctx->N, ctx->K).tk(), ctx->d_pose, ctx->d_chunks, ctx->sp, ctx->d_px, ctx->d_py, ctx->gs, ctx->icap, it0, mode,
-                     gsel.sel, ctx->select_delta, all_after, ppw, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
-                     ctx->d_ctl + b, ctx->round_list | (local ? 4 : 0) | (ctx->tail_duo ? 0 : 8) | ((ctx->scan_anchors && ctx->lipschitz_ok) ? 16 : 0), ctx->prune,
+                     gsel.sel, ctx->select_delta, kTailAllAfter, ppw, ctx->d_res_sdf, ctx->d_res_t, ctx->d_res_gx, ctx->d_res_gy,
+                     ctx->d_ctl + b, kListScans | kListCheap | (local ? kTailLocalState : 0) | (ctx->tail_duo ? 0 : kTailNoDuo) | ((ctx->scan_anchors && ctx->lipschitz_ok) ? kScanAnchors : 0), ctx->prune ? kSolvePrune : 0,
                      // a wave slot for every point at two waves per SIMD: the instantiation without scratch (k_tail, kTailLatencyWaves)
                      (ctx->tail_latency && ppw == 1 && pts <= (long long)ctx->n_cu * 4 * svsdf::kTailLatencyWaves) ? 1 : 0};
   const int shape = l.poly_lds ? (int)kPolygonLds : ctx->cfg.shape_id;
@@ -338,7 +341,7 @@ void launch_tail(svsdf_ctx *ctx, hipStream_t st, int b, int it0) {
     launch_result(ctx, launch_k_tail(shape, mode, grid, l.bytes, st, a), "k_tail");
     if (svsdf_launch_rec *r = record_launch(ctx, SVSDF_KERNEL_TAIL, compiled_shape(shape), grid, (unsigned)kTailBlock, l.bytes, pts, b)) {
       r->targ[0] = mode; r->targ[1] = a.latency ? svsdf::kTailLatencyWaves : SVSDF_TAIL_WAVES; r->iter = it0; r->points_per_wave = ppw;
-      r->local_state = local ? 1 : 0; r->duo = (ppw == 1 && ctx->tail_duo) ? 1 : 0; r->anchors = (a.clist_on & 16) ? 1 : 0;
+      r->local_state = (a.clist_on & kTailLocalState) ? 1 : 0; r->duo = (ppw == 1 && !(a.clist_on & kTailNoDuo)) ? 1 : 0; r->anchors = (a.clist_on & kScanAnchors) ? 1 : 0;
     }
     debug_sync(st, "k_tail", mode, it0);
   }
@@ -361,8 +364,7 @@ int choose_tail_iter(const svsdf_ctx *ctx) {
   if (!plan_block_lds(ctx, TableUser::Tail, tail_wave_bytes(false), false).fits) return -1;
   if (ctx->tail_mode >= 0) return std::min(ctx->tail_mode, (int)kMaxIter - 2);
   if (!ctx->have_prev_nactive) return -1;   // first evaluation of a point set: the interior count is not known yet
-  const long long below = ctx->tail_below > 0 ? ctx->tail_below : (long long)ctx->n_cu * 24;
-  return (ctx->prev_nactive[0] <= below) ? 0 : -1;
+  return (ctx->prev_nactive[0] <= tail_interior_limit(ctx)) ? 0 : -1;
 }
 
 void launch_classify(svsdf_ctx *ctx, hipStream_t st, int b) {
@@ -566,18 +568,17 @@ void enqueue_solve_round(svsdf_ctx *ctx, int it, bool tail_next = false) {
     QuerySet q{};
     q.qx = ctx->gs.sqx; q.qy = ctx->gs.sqy; q.count_ptr = &ctl->n_solve[it];
     q.slots = ctx->gs.solve + (size_t)ctx->bstart[b] * kMaxSlots; q.n_outer = 1;
-    if (ctx->ub_full) { q.seed_k = ctx->gs.sq_k; q.seed_d = ctx->gs.sq_ub; }
-    int G = (it >= ctx->late_iter) ? ctx->G_late : ctx->G;
+    if (ctx->bound_mode != 0) { q.seed_k = ctx->gs.sq_k; q.seed_d = ctx->gs.sq_ub; }   // (the stored mode: any scanning mode leaves seeds)
+    // G_late from iteration kLateIter on without counts on record; with them, the iteration's solves below which the groups widen to 32 / 16 / 8 lanes
+    constexpr int kLateIter = 4; constexpr long long kWide32Below = 2000, kWide16Below = 5000, kWide8Below = 40000;
+    int G = (it >= kLateIter) ? ctx->G_late : ctx->G;
     // Successive callbacks of one optimisation see almost the same trajectory: iteration `it` of the previous
     // evaluation tells how many solves this launch will hold.  Few solves = a latency-bound launch (<= ~1 wave per
     // SIMD): widen the groups to shorten the dependent chain; many solves = throughput: keep the shard's width even
     // in late iterations.  Any width gives the same bits, so a wrong guess only costs time.
     if (!ctx->G_env && !ctx->G_late_env && ctx->have_prev_nsolve) {
       const long long n = ctx->prev_nsolve[it];   // summed over the batches: they run this iteration concurrently
-      G = ctx->G;
-      if (n < ctx->wide32_below) G = std::max(G, 32);
-      else if (n < ctx->wide16_below) G = std::max(G, 16);
-      else if (n < ctx->wide8_below) G = std::max(G, 8);
+      G = std::max(ctx->G, n < kWide32Below ? 32 : n < kWide16Below ? 16 : n < kWide8Below ? 8 : 1);
     }
     launch_solve(ctx, G, st, q, (long long)ctx->bcount[b] * kMaxSlots, ctx->gs.sq_sdf, ctx->gs.sq_t, ctl, it + 1);
     if (tail_next) launch_tail(ctx, st, b, it + 1);
@@ -585,19 +586,20 @@ void enqueue_solve_round(svsdf_ctx *ctx, int it, bool tail_next = false) {
   }
 }
 
+// What every evaluation starts from: no profile events in use, fresh statistics and a fresh launch record.
+static void begin_evaluation(svsdf_ctx *ctx) {
+  ctx->ev_used = 0;
+  ctx->refine_events.clear(); ctx->round_events.clear(); ctx->tail_events.clear();
+  ctx->stats = svsdf_stats{}; ctx->stats.points = ctx->P;
+  reset_launches(ctx);
+}
 // Enqueue the device pipeline up to the per-point results of getTrueSDFofSweptVolume (res_*).
 // No host synchronisation: batches run on their own streams, joined back onto ctx->stream.
 int enqueue_queries(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bool allow_cull) {
   if (ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "host-only context: no device entry points");
   if (!ctx->points_set) return fail(ctx, SVSDF_ERR_NO_POINTS, "svsdf_set_points has not been called");
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->ev_used = 0;
-  ctx->refine_events.clear();
-  ctx->round_events.clear();
-  ctx->tail_events.clear();
-  ctx->stats = svsdf_stats{};
-  ctx->stats.points = ctx->P;
-  reset_launches(ctx);
+  begin_evaluation(ctx);
   const size_t e_begin = next_event(ctx);
   (void)hipEventRecord(ctx->ev_pool[e_begin], ctx->stream);
   int rc = upload_traj(ctx, N, coeffs, T, /*clear_nonfinite=*/true);   // (k_prep also clears the non-finite counter)
@@ -638,13 +640,7 @@ int swept_field(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, do
   if (!ctx->points_set) return fail(ctx, SVSDF_ERR_NO_POINTS, "svsdf_set_points has not been called");
   if (ctx->P == 0) return SVSDF_OK;
   HIPCHK(hipSetDevice(ctx->device));
-  ctx->ev_used = 0;
-  ctx->refine_events.clear();
-  ctx->round_events.clear();
-  ctx->tail_events.clear();
-  ctx->stats = svsdf_stats{};
-  ctx->stats.points = ctx->P;
-  reset_launches(ctx);
+  begin_evaluation(ctx);
   int rc = upload_traj(ctx, N, coeffs, T);
   if (rc) return rc;
   if ((rc = build_layer_tables(ctx))) return rc;
@@ -773,16 +769,13 @@ int finish(svsdf_ctx *ctx, bool with_partial) {
   ctx->stats.tail_points = (ctx->tail_iter >= 0 && ctx->tail_iter < kMaxIter) ? cnt.n_active[ctx->tail_iter] : 0ull;
   // next evaluation enqueues as many iterations as this one needed (+1); the slow path above
   // covers an underestimate
-  if (ctx->adaptive_iters && ctx->tail_iter < 0) ctx->first_iters = std::max(2, std::min((int)cnt.gsip_iterations + 1, (int)kMaxIter));
-  if (ctx->profile_span && !ctx->profile) {
+  if (ctx->tail_iter < 0) ctx->first_iters = std::max(2, std::min((int)cnt.gsip_iterations + 1, (int)kMaxIter));
+  if (ctx->profile_span || ctx->profile) {
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, ctx->ev_pool[0], ctx->ev_pool[ctx->e_end]);
     ctx->stats.device_ms = ms;
   }
   if (ctx->profile) {
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, ctx->ev_pool[0], ctx->ev_pool[ctx->e_end]);
-    ctx->stats.device_ms = ms;
     // k_solve time of the evaluation: the point batches run concurrently on their own streams, so the launches'
     // [start, stop] intervals (device clock, relative to the evaluation's first event) are merged -- solve_ms is the
     // time during which at least one k_solve launch was executing, solve_ms_sum the plain sum of the launch durations
@@ -831,7 +824,7 @@ void fill_mode_stats(svsdf_ctx *ctx) {
   ctx->stats.gsip_bound_mode = bound_mode_of(ctx);
   ctx->stats.piece_time_exact = ctx->stats_piece_time;
   ctx->stats.bound_mode_decided = (ctx->ub_env || ctx->ub_tune > 0) ? 1 : 0;
-  ctx->stats.plan_settled = (ctx->stats.bound_mode_decided && ctx->bt_state == 0 && ctx->an_state == 0 && ctx->lz_state == 0 && ctx->have_prev_nsolve) ? 1 : 0;
+  ctx->stats.plan_settled = plan_settled(ctx) ? 1 : 0;
   ctx->stats.bound_ratio = ctx->ub_ratio;
   ctx->stats.n_devices = 1;
   ctx->stats.combine = SVSDF_COMBINE_HOST;
@@ -877,18 +870,19 @@ int run_pipeline_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double 
   // evaluations per mode with the wall clock; the rule reproduces its choices on C1-C5 without the five extra
   // evaluations and without depending on the box.)
   const bool deciding = !ctx->ub_env && ctx->ub_tune == 0;
-  if (deciding) { ctx->ub_full = false; ctx->ub_lazy = false; ctx->ub_anchor = false; ctx->an_state = 0; ctx->lz_state = 0; }
+  if (deciding) { ctx->bound_mode = 0; stop_trials(ctx); }
   // Anchor trial (full-scan shapes only): one evaluation in the full mode and one in the anchor mode, compared by their
   // table-evaluation COUNTERS (deterministic: no timing) -- the anchor mode stays when it saves at least 28 % of them
   // (sdHeart - 32 %: k_round - 27 %, evaluation - 12 %; Polygon - 25 %: a wash; sdHorseshoe - 10 %: + 5 %, its extra passes
   // cost more than the skipped scans; profiles/r04_anchor_ab.txt).  Both modes return the same bits.
   const int an_trial = (ctx->ub_env || ctx->saved_nbatch > 0) ? 0 : ctx->an_state;
-  if (an_trial == 1) ctx->ub_anchor = false;
-  if (an_trial == 2) ctx->ub_anchor = true;
+  // (pending only in the full / anchor pair: started from a decision for mode 1, stopped by whatever stores another mode)
+  if (an_trial == 1) ctx->bound_mode = 1;
+  if (an_trial == 2) ctx->bound_mode = 3;
   // Lazy trial (round 5; small clouds of a cheap-bound shape only, see the deciding block below): this evaluation runs in
   // the lazy mode and is judged by its GSIP solve COUNT against the cheap bound's (deterministic, no timing).
   const int lz_trial = (ctx->ub_env || ctx->saved_nbatch > 0) ? 0 : ctx->lz_state;
-  if (lz_trial == 1) { ctx->ub_full = true; ctx->ub_lazy = true; }
+  if (lz_trial == 1) ctx->bound_mode = 2;
   // Batch count (DESIGN.md "concurrent point batches").  Default: a RULE -- 3 batches from 80 k points per device, 1 below
   // (round 5; rounds 3 - 4: from 400 k in a scanning mode only; what the measurements -- 1 / 2 / 3 / 4 at NS, C3, C4 and at
   // 60 k ... 500 k points -- chose on every box; with the main stream that is at most 4 streams, the HIP runtime's default
@@ -927,48 +921,42 @@ int run_pipeline_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double 
     ctx->an_state = 2;
   } else if (rc == SVSDF_OK && an_trial == 2) {
     const bool keep = (double)ctx->stats.round_scan_evals <= 0.72 * (double)ctx->an_full_evals;
-    if (keep != ctx->ub_anchor) { ctx->have_prev_nsolve = false; ctx->have_prev_nactive = false; }
-    ctx->ub_anchor = keep;
+    if (!keep) { forget_launch_history(ctx); ctx->bound_mode = 1; }   // (the plan on record is the anchor mode's)
     ctx->an_state = 0;
   }
+  const unsigned long long main_solves = ctx->stats.points - ctx->stats.culled_points;   // (gs: the GSIP solves of this evaluation)
+  const unsigned long long gs = ctx->stats.solves > main_solves ? ctx->stats.solves - main_solves : 0ull;
   if (lz_trial == 1) {
-    const unsigned long long main_solves = ctx->stats.points - ctx->stats.culled_points;
-    const unsigned long long gs = ctx->stats.solves > main_solves ? ctx->stats.solves - main_solves : 0ull;
     const bool keep = rc == SVSDF_OK && (double)gs <= 0.76 * (double)ctx->lz_cheap_solves;
-    if (!keep) { ctx->ub_full = false; ctx->ub_lazy = false; }
-    ctx->have_prev_nsolve = false;   // (the widths on record belong to the deciding evaluation / to the rejected mode; the interior count stands)
+    if (!keep) ctx->bound_mode = 0;
+    forget_solve_counts(ctx);   // (the widths on record belong to the deciding evaluation / to the rejected mode; the interior count stands)
     ctx->lz_state = 0;
   }
   if (rc == SVSDF_OK && deciding) {
-    const unsigned long long main_solves = ctx->stats.points - ctx->stats.culled_points;
-    const unsigned long long gs = ctx->stats.solves > main_solves ? ctx->stats.solves - main_solves : 0ull;
     ctx->ub_ratio = ctx->stats.gsip_samples ? (double)gs / (double)ctx->stats.gsip_samples : 0.0;
     // Polygon: an SDF evaluation costs several times an analytic shape's (candidate edges of the outline), a table
     // scan proportionally less of a solve, so scanning pays from a lower ratio
-    const double thr = ctx->cfg.shape_id == SVSDF_SHAPE_Polygon ? 0.2 : ctx->ub_threshold;
+    const double thr = ctx->cfg.shape_id == SVSDF_SHAPE_Polygon ? 0.2 : 0.5;
     // below the threshold a large shard still gains from scanning -- but only the samples the cheap bound would have
     // had solved (lazy mode: NS, star / 16 pieces / 1 M points, 12.3 -> 11.4 ms; at 100 k points no gain)
-    const bool large = ctx->P >= 400000;
-    ctx->ub_full = ctx->ub_ratio > thr || large;
-    ctx->ub_lazy = !(ctx->ub_ratio > thr);
+    ctx->bound_mode = (ctx->ub_ratio > thr) ? 1 : (ctx->P >= 400000) ? 2 : 0;
     // A SMALL cloud of a cheap-bound shape (round 5): when the fused tail owns the whole GSIP loop (choose_tail_iter: at most
     // 24 interior points per CU) an evaluation is a latency chain -- a scan costs lanes that idle anyway, every solve it
     // saves is a dozen dependent steps.  Whether the lazy scans save enough depends on the workload, not on the ratio above
     // (star: 16 pieces / 1 k - 10 k points - 8 ... - 20 %, the reference's star map 398 -> 367 us; 8 pieces / 10 k points
     // + 15 %: profiles/r05_small_cloud_modes.txt), so the next evaluation TRIES the lazy mode and stays in it when its GSIP
     // solves drop to <= 76 % of this evaluation's (the cases above: 68 - 72 % against 83 - 87 %).  Same bits in every mode.
-    const long long tail_below = ctx->tail_below > 0 ? ctx->tail_below : (long long)ctx->n_cu * 24;
-    if (!ctx->ub_full && ctx->tail_mode != -2 && (long long)ctx->stats.interior_points <= tail_below && gs > 0) {
+    if (ctx->bound_mode == 0 && ctx->tail_mode != -2 && (long long)ctx->stats.interior_points <= tail_interior_limit(ctx) && gs > 0) {
       ctx->lz_state = 1;
       ctx->lz_cheap_solves = gs;
     }
-    if (ctx->ub_full && !ctx->ub_lazy && ctx->lipschitz_ok) ctx->an_state = 1;   // full scans pay: does the anchor variant pay more?
-    if (ctx->ub_full) { ctx->have_prev_nsolve = false; ctx->have_prev_nactive = false; }   // the launch plan on record is the cheap-bound one
+    if (ctx->bound_mode == 1 && ctx->lipschitz_ok) ctx->an_state = 1;   // full scans pay: does the anchor variant pay more?
+    if (ctx->bound_mode != 0) forget_launch_history(ctx);   // the launch plan on record is the cheap-bound one
   }
   // the batch count follows once the bound mode is known (also when it was pinned)
   if (rc == SVSDF_OK && ctx->ub_tune == 0) {
     ctx->ub_tune = 1;
-    const bool big = ctx->ub_full && ctx->P >= 400000;
+    const bool big = ctx->bound_mode != 0 && ctx->P >= 400000;
     if (ctx->want_batches == 0) {
       // Round 5 (profiles/r05_batches_by_size.txt): 3 batches pay from ~ 80 k points per device in EVERY bound mode -- 60 k: + 2 ... 9 %,
       // 100 k: + 9 ... 14 %, 150 - 250 k: + 4 ... 16 % (star / sdHorseshoe / sdHeart; 2 batches always in between, 4 lose at
@@ -981,7 +969,7 @@ int run_pipeline_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double 
     } else if (ctx->want_batches < 0 && big) {
       ctx->bt_state = 1;
       ctx->bt_cand[0] = 1;
-      ctx->bt_cand[1] = ctx->ub_lazy ? 2 : 4;
+      ctx->bt_cand[1] = ctx->bound_mode == 2 ? 2 : 4;
       ctx->bt_cand[2] = 3;
       ctx->bt_ncand = 3;
     }
@@ -1220,22 +1208,8 @@ int take_stripe(svsdf_ctx *ctx, svsdf_ctx *planner, const CloudPlan &plan, int r
   // known, see set_batches)
   int rcb = set_batches(ctx, ctx->want_batches > 0 ? ctx->want_batches : 1);   // (rule / measurement: after the bound mode, run_pipeline_leaf)
   if (rcb) return rcb;
-  // lanes per query: an evaluation is a chain of ~10 dependent solve launches, each a chain of ~100 dependent
-  // group steps.  Small shards cannot fill the GPU and are pure latency: wide groups shorten the chains
-  // (32 lanes: a whole halving ladder / scan layer per step).  Large shards are throughput: narrow groups waste
-  // fewer lanes (2 since round 3: the ladders share the wave's lanes anyway, so the width only shapes the scan layers and
-  // the derivative).  Measured crossovers (tools/latency.py, tools/sweep.py): 3e3, 2e4, 3e5 points.
-  ctx->have_prev_nsolve = false;
-  ctx->have_prev_nactive = false;
-  ctx->prev_tail_iter = -1;
-  ctx->ub_tune = 0;
-  ctx->bt_state = 0;
-  ctx->ub_ratio = 0.0;
-  if (!ctx->ub_env) { ctx->ub_full = false; ctx->ub_lazy = false; ctx->ub_anchor = false; }
-  ctx->an_state = 0;
-  ctx->lz_state = 0;
-  if (!ctx->G_env) {
-    // (Polygon: 4 -- its 2-lane kernel spills 52 registers under the 3-waves cap; C5 36.5 vs 34.8 ms)
+  reset_plan(ctx);
+  if (!ctx->G_env) {   // lanes per query by shard size (default_lanes; Polygon: 4 -- its 2-lane kernel spills 52 registers under the 3-waves cap; C5 36.5 vs 34.8 ms)
     ctx->G = default_lanes(ctx, Ps);
     if (!ctx->G_late_env) ctx->G_late = std::max(ctx->G, 8);
   }

@@ -143,3 +143,54 @@ def test_anchor_scans_are_chosen_by_counters_and_invisible(built):
     assert f.stats()["gsip_bound_mode"] == 1 and anchor_evals <= 0.72 * f.stats()["round_scan_evals"]
     _same(got, ref, "anchor vs full")
     c.close(); f.close()
+
+
+def _five(c, w, n=5):
+    """Five evaluations: after each one the plan and the bytes of cost | gradT | gradC."""
+    out = []
+    for _ in range(n):
+        cost, gT, gC = c.eval_penalty(w["coeffs"], w["T"])
+        out.append((c.get_plan(), np.float64(cost).tobytes() + gT.tobytes() + gC.tobytes()))
+    return out
+
+
+@pytest.mark.parametrize("config,N,trial", [("C1", 8, "lazy"), ("C4", 32, "anchor")])
+def test_plan_forgets_completely(built, config, N, trial):
+    """Whatever resets the plan leaves nothing of the old one behind: after a new point set (a), and after a pinned bound
+    mode is released (b), a settled context walks through the same five plans, with the same result bytes, as a fresh
+    one.  Serialised profiling (c) is no reset: the settled plan stays as it is.  2 000 corridor points each: the star at
+    8 pieces has a tail-sized interior and goes through the lazy trial; sdHeart goes to the full scans and through the
+    anchor trial at its config's 32 pieces (at 8 pieces its first evaluation solves 1/2 of the samples or fewer and the
+    cheap bound stays, measured: no anchor trial).  Plans and bytes are compared, not launches: the enqueued iteration
+    count survives a new point set on purpose."""
+    import svsdf_amd
+    from svsdf_amd import workload
+    w = workload.make(config, P=2000, N=N, minco=svsdf_amd.minco_coeffs)
+    f = _ctx(w)
+    fresh, ran = [], []
+    for _ in range(5):
+        fresh += _five(f, w, 1)
+        ran.append({r["targ"][r["kernel"] == "round"] for r in f.last_launches() if r["kernel"] in ("round", "tail")})
+    f.close()
+    print(config, "fresh plans", [pl for pl, _ in fresh], "bound modes launched", ran)
+    # the path the case is here for ran: the first evaluation decided for the cheap bound / the full scans, and a later
+    # one launched the trial's mode (k_round's MODE is its second template argument, k_tail's its first)
+    assert ran[0] == {0} and fresh[0][0]["bound_mode"] == (0 if trial == "lazy" else 1), (fresh[0], ran)
+    assert any((2 if trial == "lazy" else 3) in m for m in ran[1:]), ran
+    assert fresh[-1][0]["settled"] == 1 and len({b for _, b in fresh}) == 1, fresh
+    c = _ctx(w)
+    assert _five(c, w) == fresh
+    c.set_points(w["points"])                                 # (a)
+    assert _five(c, w) == fresh, "set_points"
+    for k in (0, 1, 2, 3):                                    # (b)
+        c.set_plan(bound_mode=k)
+        assert c.eval_penalty(w["coeffs"], w["T"])[0] == np.frombuffer(fresh[0][1][:8])[0]
+        assert c.get_plan()["bound_mode"] == k
+        c.set_plan()
+        assert _five(c, w) == fresh, ("set_plan", k)
+    c.set_profiling(2)                                        # (c)
+    for _ in range(2):
+        c.eval_penalty(w["coeffs"], w["T"])
+    c.set_profiling(0)
+    assert _five(c, w) == [fresh[-1]] * 5, "set_profiling"
+    c.close()
