@@ -164,24 +164,21 @@ svsdf_ctx *svsdf_create(const svsdf_config *cfg) {
     const int ngf = 128, ngc = 256;   // grid cells per side, fine / coarse
     if (!build_poly_accel(v.data(), (int)(v.size() / 2), pa, ngf, ngc, 256, SVSDF_POLY_REFINE, 32, loops.empty() ? nullptr : loops.data(), (int)loops.size()))
       return bail("svsdf_create: polygon outline rejected (non-finite vertex?)");
-    auto align = [](size_t o) { return (o + 63) & ~(size_t)63; };
-    const size_t o_edges = align(sizeof(PolyAccel));
-    const size_t o_cell = align(o_edges + pa.edges.size() * sizeof(PolyEdge));
-    const size_t o_slab = align(o_cell + pa.cells.size() * sizeof(PolyRec));
-    const size_t o_over = align(o_slab + pa.slabs.size() * sizeof(PolyRec));
-    const size_t total = align(o_over + pa.over.size() * sizeof(unsigned short));
-    if (ctx->d_poly.alloc(ctx, total)) return bail("hipMalloc polygon failed");
-    std::vector<unsigned char> blob(total, 0);
-    pa.hdr.edges = reinterpret_cast<const PolyEdge *>(ctx->d_poly + o_edges);
-    pa.hdr.cells = reinterpret_cast<const PolyRec *>(ctx->d_poly + o_cell);
-    pa.hdr.slabs = reinterpret_cast<const PolyRec *>(ctx->d_poly + o_slab);
-    pa.hdr.over = reinterpret_cast<const unsigned short *>(ctx->d_poly + o_over);
-    std::memcpy(blob.data(), &pa.hdr, sizeof(PolyAccel));
-    std::memcpy(blob.data() + o_edges, pa.edges.data(), pa.edges.size() * sizeof(PolyEdge));
-    std::memcpy(blob.data() + o_cell, pa.cells.data(), pa.cells.size() * sizeof(PolyRec));
-    std::memcpy(blob.data() + o_slab, pa.slabs.data(), pa.slabs.size() * sizeof(PolyRec));
-    if (!pa.over.empty()) std::memcpy(blob.data() + o_over, pa.over.data(), pa.over.size() * sizeof(unsigned short));
-    if (hipMemcpy(ctx->d_poly, blob.data(), total, hipMemcpyHostToDevice) != hipSuccess)
+    const svsdf_layout::PolyLayout L = svsdf_layout::poly_layout(sizeof(PolyAccel), sizeof(PolyEdge), sizeof(PolyRec), pa.edges.size(),
+                                                                 pa.cells.size(), pa.slabs.size(), pa.over.size());
+    if (ctx->d_poly.alloc(ctx, L.bytes)) return bail("hipMalloc polygon failed");
+    std::vector<unsigned char> blob(L.bytes, 0);
+    // each part: its device address into the header, its records into the host image
+    const auto place = [&](auto &field, size_t off, const auto &v) {
+      field = svsdf_layout::at<std::remove_reference_t<decltype(*field)>>(ctx->d_poly.get(), off);
+      if (!v.empty()) std::memcpy(blob.data() + off, v.data(), v.size() * sizeof(v[0]));
+    };
+    place(pa.hdr.edges, L.edges, pa.edges);
+    place(pa.hdr.cells, L.cells, pa.cells);
+    place(pa.hdr.slabs, L.slabs, pa.slabs);
+    place(pa.hdr.over, L.over, pa.over);
+    std::memcpy(blob.data() + L.hdr, &pa.hdr, sizeof(PolyAccel));
+    if (hipMemcpy(ctx->d_poly, blob.data(), L.bytes, hipMemcpyHostToDevice) != hipSuccess)
       return bail("hipMemcpy polygon failed");
     sp.nverts = (int)pa.edges.size();   // entries of the edge array: the vertices + one closing copy per loop of a multi-loop outline
     sp.accel = reinterpret_cast<const PolyAccel *>(ctx->d_poly.get());
@@ -577,10 +574,10 @@ int svsdf_set_scale(svsdf_ctx *ctx, const svsdf_scale *scale) {
     }
   }
   // (the swept outline's cached result belongs to the old schedule)
-  for (svsdf_ctx *s : ctx->subs) { s->scaled = on; s->scale = d; s->ol_valid = false; }
+  for (svsdf_ctx *s : ctx->subs) { s->scaled = on; s->scale = d; s->outline.valid = false; }
   ctx->scaled = on;
   ctx->scale = d;
-  ctx->ol_valid = false;
+  ctx->outline.valid = false;
   return SVSDF_OK;
 }
 

@@ -6,7 +6,7 @@
 // Memory: every device and pinned allocation of the library is a Buf (below) -- the one place that allocates and frees.
 // A Buf frees in its destructor, on the device it allocated on, so the context, a CloudPlan and a function's scratch
 // release what they hold by going out of scope; no function keeps a list of pointers to free.  Structs that kernels take
-// by value (GsipState, AstarDev, FrontMapDev) stay raw views; their owners sit beside them in the context.
+// by value (GsipState, AstarDev, FrontMapDev) stay raw views; their owners sit beside them (gs_own, FrontMap).
 // Nothing here is part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +33,7 @@
 
 #include "../../include/svsdf_c.h"
 #include "svsdf_launch.hpp"
+#include "svsdf_layout.hpp"
 #include "svsdf_minco.hpp"
 
 // One host thread per device of an in-process multi-GPU context.
@@ -158,6 +159,37 @@ struct Staged {
   }
 };
 
+// ---- Front-end state, all of it svsdf_extras.hip's.  The packed buffers are laid out in svsdf_layout.hpp.
+// The resident map (svsdf_frontend_set_map) and what belongs to it.  Releasing it is assigning a fresh one.
+struct FrontMap {
+  bool set = false;
+  svsdf::FrontMapDev dev{};                   // what the kernels take: views of the three buffers below + geometry
+  Buf<unsigned long long> d_occ, d_free;      // inflated occupancy bitmap, yaw-free table
+  Buf<double> d_kt;
+  int Z = 0;                                  // layers of the map's grid (the search stays in layer 0)
+  // svsdf_astar_search: one device blob (svsdf_layout::astar_layout) that `astar` views; sized for this map at the first
+  // search on it
+  Buf<unsigned char> d_astar;
+  svsdf::AstarDev astar{};
+  bool searched = false;                      // the node records hold a search on this map
+};
+// Staging that outlives a map change, grown on demand
+struct FrontStaging {
+  Staged<double> edges;                       // svsdf_check_sub_sw_collision: svsdf_layout::subsw_layout
+  Buf<int> d_flag;                            // ... its hit flags, flag_cap entries, and their host copy
+  std::vector<int> h_flag;
+  size_t flag_cap = 0;
+  Staged<unsigned char> succ;                 // svsdf_astar_successors: svsdf_layout::succ_layout (97 bytes per parent)
+  PinBuf<svsdf::AstarState> h_astar;          // pinned: the search state goes up once per search and comes back once per launch
+};
+// svsdf_swept_outline: the last result, so that the documented query-then-fill protocol runs the extraction once
+struct OutlineCache {
+  std::vector<double> key, xy;
+  std::vector<int> loops;
+  svsdf_outline_stats stats{};
+  bool valid = false;
+};
+
 // Streams come from a process-wide pool and go back to it (svsdf_pipeline.hip, acquire_streams)
 struct StreamSet { hipStream_t main = nullptr; hipStream_t batch[svsdf::kMaxBatches] = {}; int slot = -1; };
 
@@ -174,7 +206,7 @@ struct svsdf_ctx {
   hipEvent_t ev_prep = nullptr, ev_done[svsdf::kMaxBatches] = {};
   svsdf::ShapeParams sp{};
   bool poly_lds = false;             // Polygon: k_solve / k_round run their kPolygonLds variants (edges at the start of LDS)
-  Buf<unsigned char> d_poly;         // Polygon: one device blob [PolyAccel | edges | cell records | slab records | long lists]
+  Buf<unsigned char> d_poly;         // Polygon: one device blob, svsdf_layout::poly_layout
   std::vector<double> poly_xy;       // Polygon: the outline as given (host copy)
   std::vector<int> poly_loops;       // Polygon: vertices per closed loop (empty: one loop)
   std::string err;
@@ -277,26 +309,9 @@ struct svsdf_ctx {
   Buf<int> d_nonfinite;
   size_t e_end = 0;
 
-  // front-end batches (row f3): growing staging [father | child | pts | kt] + offsets (doubles), and the flags
-  svsdf_impl::Staged<double> fe;
-  Buf<int> d_fe_flag;
-  std::vector<int> h_fe_flag;
-  size_t fe_edges_cap = 0;
-
-  // resident front-end map (svsdf_frontend_set_map): inflated occupancy bitmap, yaw-free table, kt table, geometry;
-  // pinned + device staging of svsdf_astar_successors [parent yaw | parent ij || child yaw | stage]
-  bool fm_set = false;
-  svsdf::FrontMapDev fm{};
-  Buf<unsigned long long> d_fm_occ, d_fm_free;
-  Buf<double> d_fm_kt;
-  svsdf_impl::Staged<unsigned char> succ;     // (97 bytes per parent)
-  // svsdf_astar_search: one device blob [state | node records | open set | path], carved up in `astar`; sized for the
-  // resident map at the first search on it, released with the map
-  Buf<unsigned char> d_astar;
-  PinBuf<svsdf::AstarState> h_astar;          // pinned: the state goes up once per search and comes back once per launch
-  int fm_Z = 0;                               // layers of the resident map's grid (the search stays in layer 0)
-  svsdf::AstarDev astar{};
-  bool astar_searched = false;                // the node records hold a search on the resident map
+  // front end (row f3; svsdf_extras.hip alone): the resident map, and the staging that outlives it
+  svsdf_impl::FrontMap fmap;
+  svsdf_impl::FrontStaging fstage;
 
   // profiling
   bool profile = false;  // per-launch HIP events (env SVSDF_PROFILE=1 or svsdf_set_profiling)
@@ -324,11 +339,7 @@ struct svsdf_ctx {
   double combine_ms = 0.0, setup_ms = 0.0, fanout_ms = 0.0;
   bool group_serial = false;        // svsdf_set_group_serial: the stripes' evaluations one after the other (diagnostic)
 
-  // svsdf_swept_outline: the last result, so that the documented query-then-fill protocol runs the extraction once
-  std::vector<double> ol_key, ol_xy;
-  std::vector<int> ol_loops;
-  svsdf_outline_stats ol_stats{};
-  bool ol_valid = false;
+  svsdf_impl::OutlineCache outline;   // svsdf_swept_outline's last result
   size_t lds_limit = 65536;         // dynamic LDS a block may ask for on this device
   std::string launch_err;           // a launch that could not be made (LDS budget, shape not compiled); reported by join_batches
 
@@ -349,6 +360,20 @@ constexpr size_t kCtlBytes = svsdf::kMaxBatches * sizeof(svsdf::BatchCtl) + kCtl
 constexpr int kRepeat = -12345;   // finish(): more interior points than capacity -- the arrays were grown, repeat the evaluation
 
 extern const char *kShapeNames[SVSDF_SHAPE_COUNT];
+
+// ---- The prologue of a device entry point.  A multi-device context owns no device state: its first stripe's context stands in.
+inline svsdf_ctx *leaf_of(svsdf_ctx *c) { return c->subs.empty() ? c : c->subs[0]; }
+// `body(leaf)` on a context that has a device; the leaf's error string becomes the group's when the body fails on it.
+// `name`: the entry point, for "<name>: no device context".
+template <typename Body>
+int on_device(svsdf_ctx *ctx, const char *name, const Body &body) {
+  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, std::string(name) + ": no device context");
+  svsdf_ctx *leaf = leaf_of(ctx);
+  if (leaf == ctx) return body(ctx);
+  const int r = on_device(leaf, name, body);
+  if (r) ctx->err = leaf->err;
+  return r;
+}
 
 // ---- The plan's helpers.  The bound mode in force: the stored one, except that the anchor mode needs a 1-Lipschitz shape SDF and runs as the full
 // mode without one (the only place that demotes).  In force (this function) is what svsdf_get_plan, fill_mode_stats

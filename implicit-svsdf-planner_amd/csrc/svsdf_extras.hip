@@ -1,6 +1,7 @@
 // svsdf_extras.hip -- C ABI of the rows around the hot path: batched front-end collision check and
 // shape byte kernels (SWM:1171-1211, SHP:386-430), query-point producer (PCSmap_manager.cpp:88-210), mesh outline, the
 // swept volume's outline and its extrusion (SWM:321-336), the in-repo L-BFGS driver (lbfgs.hpp:290-438).
+// The device entries open with on_device (svsdf_ctx.hpp); their packed buffers are laid out in svsdf_layout.hpp.
 #include "svsdf_ctx.hpp"
 #include "svsdf_lbfgs.hpp"
 #include "svsdf_mesh.hpp"
@@ -9,6 +10,7 @@
 
 using namespace svsdf;
 using namespace svsdf_impl;
+namespace lay = svsdf_layout;
 
 // yaw table of the byte kernels: for (yaw = -PI; yaw < PI; yaw += yaw_res) (SHP:400-401); PI macro of SHP:31
 static std::vector<double> shape_kernel_yaws(int kernel_count, int *loop_count) {
@@ -22,6 +24,28 @@ static std::vector<double> shape_kernel_yaws(int kernel_count, int *loop_count) 
   return yaws;
 }
 
+// The byte kernels of `yaws` (BasicShape::initShape's loop, SHP:400-428) into the caller's d_map, kernel_size^2 bytes per yaw:
+// the yaw table's upload, then k_shape_kernels.  `what` names the caller in a HIP error.  `uncompiled`: the caller's error for a
+// shape that is not compiled into the library, null to go on without one.  `then_upload` (optional) queues the caller's own
+// uploads between the table's and the launch.
+static int build_yaw_kernels(svsdf_ctx *ctx, const char *what, const char *uncompiled, const std::vector<double> &yaws,
+                             int kernel_size, double resolution, int side, double safemargin, double *d_yaw,
+                             unsigned char *d_map, const std::function<int()> &then_upload = nullptr) {
+  const int count = (int)yaws.size();
+  hipStream_t st = ctx->stream;
+  HIPCHK_AS(what, hipMemcpyAsync(d_yaw, yaws.data(), count * sizeof(double), hipMemcpyHostToDevice, st));
+  if (then_upload) {
+    int rc = then_upload();
+    if (rc) return rc;
+  }
+  const unsigned grid = (unsigned)(((size_t)kernel_size * kernel_size * count + kBlock - 1) / kBlock);
+  if (!launch_k_shape_kernels(ctx->cfg.shape_id, grid, st, ctx->sp, kernel_size, count, resolution, side, safemargin, d_yaw, d_map) &&
+      uncompiled)
+    return fail(ctx, SVSDF_ERR_INVALID, uncompiled);
+  HIPCHK_AS(what, hipGetLastError());
+  return SVSDF_OK;
+}
+
 // kt = 0, 0.02, ... by accumulated adds while kt <= 1.0 (SWM:1189)
 static int subsw_kt_table(double kt_tab[kMaxKt]) {
   int nkt = 0;
@@ -29,117 +53,118 @@ static int subsw_kt_table(double kt_tab[kMaxKt]) {
   return nkt;
 }
 
+// One output of a "size query, then fill" entry: `v`, reported in units of `per` elements, copied to `out` if `capacity` units hold it
+template <typename T> struct Out { const std::vector<T> &v; size_t per; T *out; size_t capacity; size_t *count; };
+// Reports every count.  With every output pointer given, copies them all -- or none, and returns false, when one capacity is too small.
+template <typename... T> static bool deliver(const Out<T> &...o) {
+  ((*o.count = o.v.size() / o.per), ...);
+  if (!(... && (o.out != nullptr))) return true;   // the size query
+  if (!(... && (o.capacity >= *o.count))) return false;
+  (std::copy(o.v.begin(), o.v.end(), o.out), ...);
+  return true;
+}
+
 extern "C" {
 
 // ---- front end -----------------------------------------------------------------
-int svsdf_check_sub_sw_collision(svsdf_ctx *ctx, size_t n_edges, const double *father_states,
+int svsdf_check_sub_sw_collision(svsdf_ctx *group, size_t n_edges, const double *father_states,
                                  const double *child_states, const size_t *pts_offset, const double *pts_xy,
                                  unsigned char *free_out) {
-  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_check_sub_sw_collision: no device context");
-  if (!ctx->subs.empty()) {
-    const int r = svsdf_check_sub_sw_collision(ctx->subs[0], n_edges, father_states, child_states, pts_offset, pts_xy, free_out);
-    if (r) ctx->err = ctx->subs[0]->err;
-    return r;
-  }
-  if (n_edges == 0) return SVSDF_OK;
-  if (!father_states || !child_states || !pts_offset || !free_out)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_check_sub_sw_collision: null argument");
-  const size_t total = pts_offset[n_edges];
-  if (pts_offset[0] != 0 || (total && !pts_xy))
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_check_sub_sw_collision: bad offsets");
-  size_t max_pts = 0;
-  for (size_t e = 0; e < n_edges; ++e) {
-    if (pts_offset[e + 1] < pts_offset[e]) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_check_sub_sw_collision: offsets not monotone");
-    max_pts = std::max(max_pts, pts_offset[e + 1] - pts_offset[e]);
-  }
-  if (n_edges > 0x7fffffffu || (max_pts + kSubswPoints - 1) / kSubswPoints > 65535u)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_check_sub_sw_collision: batch too large");
-  double kt_tab[kMaxKt];
-  const int nkt = subsw_kt_table(kt_tab);
-  if (total == 0) { std::memset(free_out, 1, n_edges); return SVSDF_OK; }
-  HIPCHK(hipSetDevice(ctx->device));
-  // one packed upload: [father 3E | child 3E | kt 64 | offsets E+1 (u64) | pts 2T] through a pinned staging buffer
-  const size_t need = 6 * n_edges + kMaxKt + (n_edges + 1) + 2 * total;
-  if (need > ctx->fe.cap) {
-    int rc = ctx->fe.reserve(ctx, need + need / 2);
-    if (rc) return rc;
-  }
-  if (n_edges > ctx->fe_edges_cap) {
-    int rc = ctx->d_fe_flag.alloc(ctx, 2 * n_edges);
-    if (rc) return rc;
-    ctx->fe_edges_cap = 2 * n_edges;
-    ctx->h_fe_flag.resize(2 * n_edges);
-  }
-  double *h = ctx->fe.h;
-  std::memcpy(h, father_states, 3 * n_edges * sizeof(double));
-  std::memcpy(h + 3 * n_edges, child_states, 3 * n_edges * sizeof(double));
-  std::memcpy(h + 6 * n_edges, kt_tab, kMaxKt * sizeof(double));
-  unsigned long long *h_offs = reinterpret_cast<unsigned long long *>(h + 6 * n_edges + kMaxKt);
-  for (size_t e = 0; e <= n_edges; ++e) h_offs[e] = pts_offset[e];
-  std::memcpy(h + 6 * n_edges + kMaxKt + n_edges + 1, pts_xy, 2 * total * sizeof(double));
-  double *d_father = ctx->fe.d, *d_child = d_father + 3 * n_edges, *d_kt = d_child + 3 * n_edges;
-  unsigned long long *d_offs = reinterpret_cast<unsigned long long *>(d_kt + kMaxKt);
-  double *d_pts = d_kt + kMaxKt + n_edges + 1;
-  hipStream_t st = ctx->stream;
-  HIPCHK(hipMemcpyAsync(ctx->fe.d, h, need * sizeof(double), hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(ctx->d_fe_flag, 0, n_edges * sizeof(int), st));   // hit flags: 1 = some sdf < 0
-  const dim3 grid((unsigned)n_edges, (unsigned)((max_pts + kSubswPoints - 1) / kSubswPoints));
-  (void)launch_k_subsw(ctx->cfg.shape_id, grid, st, ctx->sp, d_father, d_child, d_offs, d_pts, d_kt, nkt, ctx->d_fe_flag);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(ctx->h_fe_flag.data(), ctx->d_fe_flag, n_edges * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  for (size_t e = 0; e < n_edges; ++e) free_out[e] = ctx->h_fe_flag[e] ? 0 : 1;
-  return SVSDF_OK;
+  return on_device(group, __func__, [&](svsdf_ctx *ctx) -> int {
+    if (n_edges == 0) return SVSDF_OK;
+    if (!father_states || !child_states || !pts_offset || !free_out)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_check_sub_sw_collision: null argument");
+    const size_t total = pts_offset[n_edges];
+    if (pts_offset[0] != 0 || (total && !pts_xy))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_check_sub_sw_collision: bad offsets");
+    size_t max_pts = 0;
+    for (size_t e = 0; e < n_edges; ++e) {
+      if (pts_offset[e + 1] < pts_offset[e]) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_check_sub_sw_collision: offsets not monotone");
+      max_pts = std::max(max_pts, pts_offset[e + 1] - pts_offset[e]);
+    }
+    if (n_edges > 0x7fffffffu || (max_pts + kSubswPoints - 1) / kSubswPoints > 65535u)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_check_sub_sw_collision: batch too large");
+    double kt_tab[kMaxKt];
+    const int nkt = subsw_kt_table(kt_tab);
+    if (total == 0) { std::memset(free_out, 1, n_edges); return SVSDF_OK; }
+    HIPCHK(hipSetDevice(ctx->device));
+    // one packed upload through a pinned staging buffer
+    const lay::SubswLayout L = lay::subsw_layout(n_edges, total, kMaxKt);
+    const size_t need = L.bytes / sizeof(double);
+    FrontStaging &fs = ctx->fstage;
+    if (need > fs.edges.cap) {
+      int rc = fs.edges.reserve(ctx, need + need / 2);
+      if (rc) return rc;
+    }
+    if (n_edges > fs.flag_cap) {
+      int rc = fs.d_flag.alloc(ctx, 2 * n_edges);
+      if (rc) return rc;
+      fs.flag_cap = 2 * n_edges;
+      fs.h_flag.resize(2 * n_edges);
+    }
+    double *h = fs.edges.h, *d = fs.edges.d;
+    std::memcpy(lay::at<double>(h, L.father), father_states, 3 * n_edges * sizeof(double));
+    std::memcpy(lay::at<double>(h, L.child), child_states, 3 * n_edges * sizeof(double));
+    std::memcpy(lay::at<double>(h, L.kt), kt_tab, kMaxKt * sizeof(double));
+    unsigned long long *h_offs = lay::at<unsigned long long>(h, L.offs);
+    for (size_t e = 0; e <= n_edges; ++e) h_offs[e] = pts_offset[e];
+    std::memcpy(lay::at<double>(h, L.pts), pts_xy, 2 * total * sizeof(double));
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipMemcpyAsync(d, h, L.bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(fs.d_flag, 0, n_edges * sizeof(int), st));   // hit flags: 1 = some sdf < 0
+    const dim3 grid((unsigned)n_edges, (unsigned)((max_pts + kSubswPoints - 1) / kSubswPoints));
+    (void)launch_k_subsw(ctx->cfg.shape_id, grid, st, ctx->sp, lay::at<double>(d, L.father), lay::at<double>(d, L.child),
+                         lay::at<unsigned long long>(d, L.offs), lay::at<double>(d, L.pts), lay::at<double>(d, L.kt), nkt, fs.d_flag);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(fs.h_flag.data(), fs.d_flag, n_edges * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const int *hit = fs.h_flag.data();
+    unsigned char *out = free_out;   // (locals: byte stores through the captured pointer would reload it every time)
+    for (size_t e = 0; e < n_edges; ++e) out[e] = hit[e] ? 0 : 1;
+    return SVSDF_OK;
+  });
 }
 
-int svsdf_shape_kernels(svsdf_ctx *ctx, int kernel_size, int kernel_count, double kernel_resolution,
+int svsdf_shape_kernels(svsdf_ctx *group, int kernel_size, int kernel_count, double kernel_resolution,
                         double safemargin, unsigned char *map_out, unsigned char *bytes_out, double *yaw_out,
                         int *loop_count) {
-  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_shape_kernels: no device context");
-  if (!ctx->subs.empty()) {
-    const int r = svsdf_shape_kernels(ctx->subs[0], kernel_size, kernel_count, kernel_resolution, safemargin, map_out,
-                                      bytes_out, yaw_out, loop_count);
-    if (r) ctx->err = ctx->subs[0]->err;
-    return r;
-  }
-  if (kernel_size <= 0 || kernel_count <= 0 || kernel_size > 4096 || kernel_count > 65536 || !map_out)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_shape_kernels: bad argument");
-  if (ctx->cfg.shape_id == SVSDF_SHAPE_Polygon)
-    return fail(ctx, SVSDF_ERR_INVALID,
-                "svsdf_shape_kernels: Polygon has no getonlySDF(pos_rel, Matrix3d) in the reference (Shape.hpp:1477)");
-  int ind = 0;
-  const std::vector<double> yaws = shape_kernel_yaws(kernel_count, &ind);
-  if (loop_count) *loop_count = ind;
-  const int count = (int)yaws.size();
-  const int size_side = (int)(0.5 * (kernel_size - 1));
-  const size_t cells = (size_t)kernel_size * kernel_size;
-  HIPCHK(hipSetDevice(ctx->device));
-  // (an early return below frees the scratch, and the owner's free waits for the device: nothing queued on the stream still reads
-  // yaws -- declared before d_yaw, so destroyed after it -- or writes map_out once this function has returned)
-  Buf<double> d_yaw;
-  Buf<unsigned char> d_map;
-  int rc = d_yaw.alloc(ctx, count);
-  if (rc == SVSDF_OK) rc = d_map.alloc(ctx, cells * count);
-  if (rc) return rc;
-  hipStream_t st = ctx->stream;
-  HIPCHK_AS("svsdf_shape_kernels", hipMemcpyAsync(d_yaw, yaws.data(), count * sizeof(double), hipMemcpyHostToDevice, st));
-  const unsigned grid = (unsigned)((cells * count + kBlock - 1) / kBlock);
-  (void)launch_k_shape_kernels(ctx->cfg.shape_id, grid, st, ctx->sp, kernel_size, count, kernel_resolution, size_side,
-                               safemargin, d_yaw, d_map);
-  HIPCHK_AS("svsdf_shape_kernels", hipGetLastError());
-  HIPCHK_AS("svsdf_shape_kernels", hipMemcpyAsync(map_out, d_map, cells * count, hipMemcpyDeviceToHost, st));
-  HIPCHK_AS("svsdf_shape_kernels", hipStreamSynchronize(st));
-  if (yaw_out) std::memcpy(yaw_out, yaws.data(), count * sizeof(double));
-  if (bytes_out) {  // byteShapeKernel::generateByteKernel SHP:194-216, or_mask SHP:95
-    const int bpl = (kernel_size + 7) / 8;
-    std::memset(bytes_out, 0, (size_t)count * kernel_size * bpl);
-    for (int k = 0; k < count; ++k)
-      for (int a = 0; a < kernel_size; ++a)
-        for (int b = 0; b < kernel_size; ++b)
-          if (map_out[(size_t)k * cells + (size_t)a * kernel_size + b])
-            bytes_out[((size_t)k * kernel_size + a) * bpl + b / 8] |= (unsigned char)(0x80u >> (b % 8));
-  }
-  return SVSDF_OK;
+  return on_device(group, __func__, [&](svsdf_ctx *ctx) -> int {
+    if (kernel_size <= 0 || kernel_count <= 0 || kernel_size > 4096 || kernel_count > 65536 || !map_out)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_shape_kernels: bad argument");
+    if (ctx->cfg.shape_id == SVSDF_SHAPE_Polygon)
+      return fail(ctx, SVSDF_ERR_INVALID,
+                  "svsdf_shape_kernels: Polygon has no getonlySDF(pos_rel, Matrix3d) in the reference (Shape.hpp:1477)");
+    int ind = 0;
+    const std::vector<double> yaws = shape_kernel_yaws(kernel_count, &ind);
+    if (loop_count) *loop_count = ind;
+    const int count = (int)yaws.size();
+    const int size_side = (int)(0.5 * (kernel_size - 1));
+    const size_t cells = (size_t)kernel_size * kernel_size;
+    HIPCHK(hipSetDevice(ctx->device));
+    // (an early return below frees the scratch, and the owner's free waits for the device: nothing queued on the stream still reads
+    // yaws -- declared before d_yaw, so destroyed after it -- or writes map_out once this function has returned)
+    Buf<double> d_yaw;
+    Buf<unsigned char> d_map;
+    int rc = d_yaw.alloc(ctx, count);
+    if (rc == SVSDF_OK) rc = d_map.alloc(ctx, cells * count);
+    if (rc == SVSDF_OK)
+      rc = build_yaw_kernels(ctx, "svsdf_shape_kernels", nullptr, yaws, kernel_size, kernel_resolution, size_side, safemargin, d_yaw, d_map);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    HIPCHK_AS("svsdf_shape_kernels", hipMemcpyAsync(map_out, d_map, cells * count, hipMemcpyDeviceToHost, st));
+    HIPCHK_AS("svsdf_shape_kernels", hipStreamSynchronize(st));
+    if (yaw_out) std::memcpy(yaw_out, yaws.data(), count * sizeof(double));
+    if (bytes_out) {  // byteShapeKernel::generateByteKernel SHP:194-216, or_mask SHP:95
+      const int bpl = (kernel_size + 7) / 8;
+      std::memset(bytes_out, 0, (size_t)count * kernel_size * bpl);
+      for (int k = 0; k < count; ++k)
+        for (int a = 0; a < kernel_size; ++a)
+          for (int b = 0; b < kernel_size; ++b)
+            if (map_out[(size_t)k * cells + (size_t)a * kernel_size + b])
+              bytes_out[((size_t)k * kernel_size + a) * bpl + b / 8] |= (unsigned char)(0x80u >> (b % 8));
+    }
+    return SVSDF_OK;
+  });
 }
 
 // ---- query-point producer (host) -----------------------------------------------------------------
@@ -169,138 +194,110 @@ int svsdf_map_gather(const svsdf_map *map, const double *centres_xyz, size_t nce
   if (!map || (!centres_xyz && ncentres) || !halfbd || !count) return SVSDF_ERR_INVALID;
   std::vector<double> pts;
   map->m.gather(centres_xyz, ncentres, halfbd, pts);
-  *count = pts.size() / 3;
-  if (out_xyz) {
-    if (capacity < *count) return SVSDF_ERR_INVALID;
-    std::copy(pts.begin(), pts.end(), out_xyz);
-  }
-  return SVSDF_OK;
+  return deliver(Out<double>{pts, 3, out_xyz, capacity, count}) ? SVSDF_OK : SVSDF_ERR_INVALID;
 }
 int svsdf_pcd_read_ascii(const char *path, float *xyz, size_t capacity, size_t *n) {
   if (!path || !n) return SVSDF_ERR_INVALID;
   std::vector<float> v;
   if (!svsdf_host::read_pcd_ascii(path, v)) return SVSDF_ERR_INVALID;
-  *n = v.size() / 3;
-  if (xyz) {
-    if (capacity < *n) return SVSDF_ERR_INVALID;
-    std::copy(v.begin(), v.end(), xyz);
-  }
-  return SVSDF_OK;
+  return deliver(Out<float>{v, 3, xyz, capacity, n}) ? SVSDF_OK : SVSDF_ERR_INVALID;
 }
 
 // ---- front end: resident map, yaw-free table, batched successor test ---------------------------------------------
-static void frontend_release(svsdf_ctx *ctx) {
-  ctx->fm_set = false;
-  ctx->d_fm_occ.reset();
-  ctx->d_fm_free.reset();
-  ctx->d_fm_kt.reset();
-  ctx->d_astar.reset();   // the search state belongs to the map
-  ctx->astar = AstarDev{};
-  ctx->astar_searched = false;
-}
+int svsdf_frontend_set_map(svsdf_ctx *group, const svsdf_map *map, int kernel_size, int kernel_count, double safemargin) {
+  return on_device(group, __func__, [&](svsdf_ctx *ctx) -> int {
+    if (!map) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: null map");
+    if (ctx->cfg.shape_id == SVSDF_SHAPE_Polygon)
+      return fail(ctx, SVSDF_ERR_INVALID,
+                  "svsdf_frontend_set_map: Polygon has no getonlySDF(pos_rel, Matrix3d) in the reference (Shape.hpp:1477), so no yaw kernels");
+    if (kernel_size <= 0 || kernel_size % 2 == 0)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: kernel_size must be odd and positive");
+    if (kernel_size > kMaxKernelSize || kernel_count > kMaxKernelCount || kernel_count < 1)
+      return fail(ctx, SVSDF_ERR_INVALID,
+                  "svsdf_frontend_set_map: kernel_size <= 63 and 1 <= kernel_count <= 64 (a kernel row and a cell's mask are one word each)");
+    if (!std::isfinite(safemargin)) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: safemargin not finite");
+    const svsdf_host::OccupancyMap &m = map->m;
+    const int X = m.dims()[0], Y = m.dims()[1], Z = m.dims()[2];
+    const int side = (kernel_size - 1) / 2;
+    if (X < 1 || Y < 1 || Z < 1) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: empty map");
+    if ((Y + kYawFreeBlock - 1) / kYawFreeBlock > 65535 || (long long)X * Y > 0x7fffffffll)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: map too large");
+    int loops = 0;
+    const std::vector<double> yaws = shape_kernel_yaws(kernel_count, &loops);
+    if ((int)yaws.size() != kernel_count)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: the reference's yaw loop yields fewer kernels than kernel_count");
+    // generateMapKernel2D (PCSmap_manager.h:81-108) in 64-bit row words: layer iz = 0, cell (x, y) at (x + side, y + side)
+    const int row_words = (Y + 2 * side + 63) / 64 + 1;
+    const size_t rows = (size_t)X + 2 * (size_t)side;
+    std::vector<unsigned long long> occ(rows * row_words, 0ull);
+    for (int x = 0; x < X; ++x)
+      for (int y = 0; y < Y; ++y)
+        if (m.cell(x, y, 0)) occ[(size_t)(x + side) * row_words + ((y + side) >> 6)] |= 1ull << ((y + side) & 63);
+    double kt_tab[kMaxKt];
+    const int nkt = subsw_kt_table(kt_tab);
 
-int svsdf_frontend_set_map(svsdf_ctx *ctx, const svsdf_map *map, int kernel_size, int kernel_count, double safemargin) {
-  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_frontend_set_map: no device context");
-  if (!ctx->subs.empty()) {
-    const int r = svsdf_frontend_set_map(ctx->subs[0], map, kernel_size, kernel_count, safemargin);
-    if (r) ctx->err = ctx->subs[0]->err;
-    return r;
-  }
-  if (!map) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: null map");
-  if (ctx->cfg.shape_id == SVSDF_SHAPE_Polygon)
-    return fail(ctx, SVSDF_ERR_INVALID,
-                "svsdf_frontend_set_map: Polygon has no getonlySDF(pos_rel, Matrix3d) in the reference (Shape.hpp:1477), so no yaw kernels");
-  if (kernel_size <= 0 || kernel_size % 2 == 0)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: kernel_size must be odd and positive");
-  if (kernel_size > kMaxKernelSize || kernel_count > kMaxKernelCount || kernel_count < 1)
-    return fail(ctx, SVSDF_ERR_INVALID,
-                "svsdf_frontend_set_map: kernel_size <= 63 and 1 <= kernel_count <= 64 (a kernel row and a cell's mask are one word each)");
-  if (!std::isfinite(safemargin)) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: safemargin not finite");
-  const svsdf_host::OccupancyMap &m = map->m;
-  const int X = m.dims()[0], Y = m.dims()[1], Z = m.dims()[2];
-  const int side = (kernel_size - 1) / 2;
-  if (X < 1 || Y < 1 || Z < 1) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: empty map");
-  if ((Y + kYawFreeBlock - 1) / kYawFreeBlock > 65535 || (long long)X * Y > 0x7fffffffll)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: map too large");
-  int loops = 0;
-  const std::vector<double> yaws = shape_kernel_yaws(kernel_count, &loops);
-  if ((int)yaws.size() != kernel_count)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: the reference's yaw loop yields fewer kernels than kernel_count");
-  // generateMapKernel2D (PCSmap_manager.h:81-108) in 64-bit row words: layer iz = 0, cell (x, y) at (x + side, y + side)
-  const int row_words = (Y + 2 * side + 63) / 64 + 1;
-  const size_t rows = (size_t)X + 2 * (size_t)side;
-  std::vector<unsigned long long> occ(rows * row_words, 0ull);
-  for (int x = 0; x < X; ++x)
-    for (int y = 0; y < Y; ++y)
-      if (m.cell(x, y, 0)) occ[(size_t)(x + side) * row_words + ((y + side) >> 6)] |= 1ull << ((y + side) & 63);
-  double kt_tab[kMaxKt];
-  const int nkt = subsw_kt_table(kt_tab);
-
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  frontend_release(ctx);
-  const size_t cells = (size_t)kernel_size * kernel_size;
-  Buf<double> d_yaw;
-  Buf<unsigned char> d_bytes;
-  Buf<unsigned long long> d_krows;
-  hipStream_t st = ctx->stream;
-  const auto build = [&]() -> int {
-    int rc = d_yaw.alloc(ctx, kernel_count);
-    if (rc == SVSDF_OK) rc = d_bytes.alloc(ctx, cells * kernel_count);
-    if (rc == SVSDF_OK) rc = d_krows.alloc(ctx, (size_t)kernel_size * kernel_count);
-    if (rc == SVSDF_OK) rc = ctx->d_fm_occ.alloc(ctx, occ.size());
-    if (rc == SVSDF_OK) rc = ctx->d_fm_free.alloc(ctx, (size_t)X * Y);
-    if (rc == SVSDF_OK) rc = ctx->d_fm_kt.alloc(ctx, kMaxKt);
-    if (rc) return rc;
-    HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(d_yaw, yaws.data(), kernel_count * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(ctx->d_fm_occ, occ.data(), occ.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(ctx->d_fm_kt, kt_tab, kMaxKt * sizeof(double), hipMemcpyHostToDevice, st));
-    // the kernel resolution is the map's: kernelConv overlays kernel cells on map cells one to one
-    const unsigned grid = (unsigned)((cells * kernel_count + kBlock - 1) / kBlock);
-    if (!launch_k_shape_kernels(ctx->cfg.shape_id, grid, st, ctx->sp, kernel_size, kernel_count, m.resolution(), side,
-                                safemargin, d_yaw, d_bytes))
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: shape not compiled into this library");
-    HIPCHK_AS("svsdf_frontend_set_map", hipGetLastError());
-    launch_k_pack_kernel_rows(st, d_bytes, kernel_size, kernel_count, d_krows);
-    HIPCHK_AS("svsdf_frontend_set_map", hipGetLastError());
-    launch_k_yaw_free(st, ctx->d_fm_occ, row_words, d_krows, kernel_size, kernel_count, X, Y, ctx->d_fm_free);
-    HIPCHK_AS("svsdf_frontend_set_map", hipGetLastError());
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    FrontMap &fm = ctx->fmap;
+    fm = FrontMap{};   // the old map goes, and its search state with it
+    Buf<double> d_yaw;
+    Buf<unsigned char> d_bytes;
+    Buf<unsigned long long> d_krows;
+    hipStream_t st = ctx->stream;
+    const auto build = [&]() -> int {
+      int rc = d_yaw.alloc(ctx, kernel_count);
+      if (rc == SVSDF_OK) rc = d_bytes.alloc(ctx, (size_t)kernel_size * kernel_size * kernel_count);
+      if (rc == SVSDF_OK) rc = d_krows.alloc(ctx, (size_t)kernel_size * kernel_count);
+      if (rc == SVSDF_OK) rc = fm.d_occ.alloc(ctx, occ.size());
+      if (rc == SVSDF_OK) rc = fm.d_free.alloc(ctx, (size_t)X * Y);
+      if (rc == SVSDF_OK) rc = fm.d_kt.alloc(ctx, kMaxKt);
+      if (rc) return rc;
+      // the kernel resolution is the map's: kernelConv overlays kernel cells on map cells one to one
+      rc = build_yaw_kernels(ctx, "svsdf_frontend_set_map", "svsdf_frontend_set_map: shape not compiled into this library", yaws,
+                             kernel_size, m.resolution(), side, safemargin, d_yaw, d_bytes, [&]() -> int {
+        HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(fm.d_occ, occ.data(), occ.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+        HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(fm.d_kt, kt_tab, kMaxKt * sizeof(double), hipMemcpyHostToDevice, st));
+        return SVSDF_OK;
+      });
+      if (rc) return rc;
+      launch_k_pack_kernel_rows(st, d_bytes, kernel_size, kernel_count, d_krows);
+      HIPCHK_AS("svsdf_frontend_set_map", hipGetLastError());
+      launch_k_yaw_free(st, fm.d_occ, row_words, d_krows, kernel_size, kernel_count, X, Y, fm.d_free);
+      HIPCHK_AS("svsdf_frontend_set_map", hipGetLastError());
+      return SVSDF_OK;
+    };
+    int rc = build();
+    // on every path: the pageable sources above and the scratch must outlive what the stream still does with them
+    const hipError_t es = hipStreamSynchronize(st);
+    if (rc == SVSDF_OK && es != hipSuccess)
+      rc = fail(ctx, SVSDF_ERR_HIP_BASE + (int)es, std::string("svsdf_frontend_set_map: ") + hipGetErrorString(es));
+    if (rc) { fm = FrontMap{}; return rc; }
+    FrontMapDev &dev = fm.dev;
+    dev.occ = fm.d_occ; dev.free_ = fm.d_free; dev.kt = fm.d_kt; dev.nkt = nkt;
+    dev.X = X; dev.Y = Y; dev.side = side; dev.row_words = row_words; dev.kernel_count = kernel_count;
+    dev.res = m.resolution();
+    dev.half = (double)(kernel_size / 2 + 1);   // front_end_Astar.hpp:224: integer division, metres
+    for (int d = 0; d < 3; ++d) { dev.bmin[d] = m.bmin()[d]; dev.bmax[d] = m.bmax()[d]; }
+    fm.Z = Z;
+    fm.set = true;
     return SVSDF_OK;
-  };
-  int rc = build();
-  // on every path: the pageable sources above and the scratch must outlive what the stream still does with them
-  const hipError_t es = hipStreamSynchronize(st);
-  if (rc == SVSDF_OK && es != hipSuccess)
-    rc = fail(ctx, SVSDF_ERR_HIP_BASE + (int)es, std::string("svsdf_frontend_set_map: ") + hipGetErrorString(es));
-  if (rc) { frontend_release(ctx); return rc; }
-  FrontMapDev &fm = ctx->fm;
-  fm.occ = ctx->d_fm_occ; fm.free_ = ctx->d_fm_free; fm.kt = ctx->d_fm_kt; fm.nkt = nkt;
-  fm.X = X; fm.Y = Y; fm.side = side; fm.row_words = row_words; fm.kernel_count = kernel_count;
-  fm.res = m.resolution();
-  fm.half = (double)(kernel_size / 2 + 1);   // front_end_Astar.hpp:224: integer division, metres
-  for (int d = 0; d < 3; ++d) { fm.bmin[d] = m.bmin()[d]; fm.bmax[d] = m.bmax()[d]; }
-  ctx->fm_Z = Z;
-  ctx->fm_set = true;
-  return SVSDF_OK;
+  });
 }
 
-int svsdf_frontend_yaw_free(const svsdf_ctx *cctx, unsigned long long *mask_out, size_t capacity, int dims2[2]) {
-  svsdf_ctx *ctx = const_cast<svsdf_ctx *>(cctx);   // (the error string is the only thing written)
-  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_frontend_yaw_free: no device context");
-  if (!ctx->subs.empty()) {
-    const int r = svsdf_frontend_yaw_free(ctx->subs[0], mask_out, capacity, dims2);
-    if (r) ctx->err = ctx->subs[0]->err;
-    return r;
-  }
-  if (!ctx->fm_set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_yaw_free: no map (svsdf_frontend_set_map)");
-  if (dims2) { dims2[0] = ctx->fm.X; dims2[1] = ctx->fm.Y; }
-  if (!mask_out) return SVSDF_OK;
-  const size_t n = (size_t)ctx->fm.X * ctx->fm.Y;
-  if (capacity < n) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_yaw_free: capacity too small (query with mask_out = NULL first)");
-  HIPCHK(hipSetDevice(ctx->device));
-  HIPCHK(hipMemcpyAsync(mask_out, ctx->d_fm_free, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return SVSDF_OK;
+int svsdf_frontend_yaw_free(const svsdf_ctx *group, unsigned long long *mask_out, size_t capacity, int dims2[2]) {
+  // (const: the error string is the only thing written)
+  return on_device(const_cast<svsdf_ctx *>(group), __func__, [&](svsdf_ctx *ctx) -> int {
+    const FrontMap &fm = ctx->fmap;
+    if (!fm.set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_yaw_free: no map (svsdf_frontend_set_map)");
+    if (dims2) { dims2[0] = fm.dev.X; dims2[1] = fm.dev.Y; }
+    if (!mask_out) return SVSDF_OK;
+    const size_t n = (size_t)fm.dev.X * fm.dev.Y;
+    if (capacity < n) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_yaw_free: capacity too small (query with mask_out = NULL first)");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(mask_out, fm.d_free, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SVSDF_OK;
+  });
 }
 
 int svsdf_kernel_bfs(unsigned long long free_mask, int kernel_count, double father_yaw, double *child_yaw, int *kernel_index) {
@@ -308,59 +305,54 @@ int svsdf_kernel_bfs(unsigned long long free_mask, int kernel_count, double fath
   return kernel_bfs(free_mask, kernel_count, father_yaw, child_yaw, kernel_index);
 }
 
-int svsdf_astar_successors(svsdf_ctx *ctx, size_t n, const int *parent_ij, const double *parent_yaw, unsigned char *ok_out,
+int svsdf_astar_successors(svsdf_ctx *group, size_t n, const int *parent_ij, const double *parent_yaw, unsigned char *ok_out,
                            double *child_yaw_out, unsigned char *stage_out) {
-  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_astar_successors: no device context");
-  if (!ctx->subs.empty()) {
-    const int r = svsdf_astar_successors(ctx->subs[0], n, parent_ij, parent_yaw, ok_out, child_yaw_out, stage_out);
-    if (r) ctx->err = ctx->subs[0]->err;
-    return r;
-  }
-  if (!ctx->fm_set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: no map (svsdf_frontend_set_map)");
-  if (n == 0) return SVSDF_OK;
-  if (!parent_ij || !parent_yaw || !ok_out || !child_yaw_out)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: null argument");
-  const FrontMapDev &fm = ctx->fm;
-  for (size_t p = 0; p < n; ++p) {
-    const int i = parent_ij[2 * p], j = parent_ij[2 * p + 1];
-    if (i < 0 || i >= fm.X || j < 0 || j >= fm.Y)
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: parent " + std::to_string(p) + " is outside the map");
-    double cy;
-    int ki;
-    if (kernel_bfs(0ull, fm.kernel_count, parent_yaw[p], &cy, &ki) < 0)
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: yaw of parent " + std::to_string(p) +
-                                              " maps to a kernel index outside [0, kernel_count)");
-  }
-  HIPCHK(hipSetDevice(ctx->device));
-  constexpr size_t kSuccParents = (size_t)1 << 18;       // parents per launch: 9 blocks each, well inside one grid dimension
-  constexpr size_t kIn = 16, kOut = 81;            // bytes per parent: yaw + ij | 9 child yaws + 9 stages
-  const size_t want = std::min(n, kSuccParents);
-  if (want * (kIn + kOut) > ctx->succ.cap) {
-    int rc = ctx->succ.reserve(ctx, std::min(kSuccParents, want + want / 2) * (kIn + kOut));
-    if (rc) return rc;
-  }
-  hipStream_t st = ctx->stream;
-  for (size_t p0 = 0; p0 < n; p0 += kSuccParents) {
-    const size_t m = std::min(kSuccParents, n - p0);
-    // one upload [yaw m (f64) | ij 2m (i32)], one read-back [child yaw 9m (f64) | stage 9m (u8)]
-    unsigned char *h = ctx->succ.h, *d = ctx->succ.d;
-    std::memcpy(h, parent_yaw + p0, m * sizeof(double));
-    std::memcpy(h + 8 * m, parent_ij + 2 * p0, 2 * m * sizeof(int));
-    HIPCHK(hipMemcpyAsync(d, h, kIn * m, hipMemcpyHostToDevice, st));
-    double *d_yaw_out = reinterpret_cast<double *>(d + kIn * m);
-    unsigned char *d_stage = d + kIn * m + 72 * m;
-    if (!launch_k_succ(ctx->cfg.shape_id, (unsigned)(9 * m), st, ctx->sp, fm, reinterpret_cast<const int *>(d + 8 * m),
-                       reinterpret_cast<const double *>(d), d_yaw_out, d_stage))
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: shape not compiled into this library");
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h + kIn * m, d + kIn * m, kOut * m, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::memcpy(child_yaw_out + 9 * p0, h + kIn * m, 72 * m);
-    const unsigned char *hs = h + kIn * m + 72 * m;
-    for (size_t e = 0; e < 9 * m; ++e) ok_out[9 * p0 + e] = hs[e] == 0 ? 1 : 0;
-    if (stage_out) std::memcpy(stage_out + 9 * p0, hs, 9 * m);
-  }
-  return SVSDF_OK;
+  return on_device(group, __func__, [&](svsdf_ctx *ctx) -> int {
+    if (!ctx->fmap.set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: no map (svsdf_frontend_set_map)");
+    if (n == 0) return SVSDF_OK;
+    if (!parent_ij || !parent_yaw || !ok_out || !child_yaw_out)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: null argument");
+    const FrontMapDev &fm = ctx->fmap.dev;
+    for (size_t p = 0; p < n; ++p) {
+      const int i = parent_ij[2 * p], j = parent_ij[2 * p + 1];
+      if (i < 0 || i >= fm.X || j < 0 || j >= fm.Y)
+        return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: parent " + std::to_string(p) + " is outside the map");
+      double cy;
+      int ki;
+      if (kernel_bfs(0ull, fm.kernel_count, parent_yaw[p], &cy, &ki) < 0)
+        return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: yaw of parent " + std::to_string(p) +
+                                                " maps to a kernel index outside [0, kernel_count)");
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    constexpr size_t kSuccParents = (size_t)1 << 18;       // parents per launch: 9 blocks each, well inside one grid dimension
+    Staged<unsigned char> &succ = ctx->fstage.succ;
+    const size_t want = std::min(n, kSuccParents);
+    if (lay::succ_layout(want).bytes > succ.cap) {
+      int rc = succ.reserve(ctx, lay::succ_layout(std::min(kSuccParents, want + want / 2)).bytes);
+      if (rc) return rc;
+    }
+    hipStream_t st = ctx->stream;
+    for (size_t p0 = 0; p0 < n; p0 += kSuccParents) {
+      const size_t m = std::min(kSuccParents, n - p0);
+      const lay::SuccLayout L = lay::succ_layout(m);   // one upload [yaw | ij], one read-back [child yaw | stage]
+      unsigned char *h = succ.h, *d = succ.d;
+      std::memcpy(h + L.yaw, parent_yaw + p0, m * sizeof(double));
+      std::memcpy(h + L.ij, parent_ij + 2 * p0, 2 * m * sizeof(int));
+      HIPCHK(hipMemcpyAsync(d, h, L.in_bytes(), hipMemcpyHostToDevice, st));
+      if (!launch_k_succ(ctx->cfg.shape_id, (unsigned)(9 * m), st, ctx->sp, fm, lay::at<const int>(d, L.ij),
+                         lay::at<const double>(d, L.yaw), lay::at<double>(d, L.child_yaw), d + L.stage))
+        return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_successors: shape not compiled into this library");
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(h + L.child_yaw, d + L.child_yaw, L.out_bytes(), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      std::memcpy(child_yaw_out + 9 * p0, h + L.child_yaw, 9 * m * sizeof(double));
+      const unsigned char *hs = h + L.stage;
+      unsigned char *ok = ok_out + 9 * p0;   // (a local: byte stores through the captured pointer would reload it every time)
+      for (size_t e = 0; e < 9 * m; ++e) ok[e] = hs[e] == 0 ? 1 : 0;
+      if (stage_out) std::memcpy(stage_out + 9 * p0, hs, 9 * m);
+    }
+    return SVSDF_OK;
+  });
 }
 
 // ---- A* search on the resident map ----------------------------------------------------------------------------------
@@ -371,29 +363,26 @@ void svsdf_astar_params_default(svsdf_astar_params *p) {
   p->start_yaw = 0.0;   // front_end_Astar.hpp:281
 }
 
-// one device blob: [state | g f yaw | open keys, seqs, path yaws | father, open cells, path cells | id]
+// the search's device blob for the resident map, at the first search on it (svsdf_layout::astar_layout), and the pinned state
 static int astar_alloc(svsdf_ctx *ctx) {
-  if (ctx->d_astar) return SVSDF_OK;
-  const size_t cells = (size_t)ctx->fm.X * ctx->fm.Y, cap = cells + 1;
-  if (cap > 0x7fffffffull) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: map too large");
-  const size_t head = 256;
-  const size_t bytes = head + 8 * (3 * cells + 3 * cap) + 4 * (cells + 2 * cap) + cells;
-  int rc = ctx->d_astar.alloc(ctx, bytes);
-  if (rc == SVSDF_OK && !ctx->h_astar) rc = ctx->h_astar.alloc(ctx, 1);
+  FrontMap &fm = ctx->fmap;
+  if (fm.d_astar) return SVSDF_OK;
+  const lay::AstarLayout L = lay::astar_layout((size_t)fm.dev.X * fm.dev.Y);
+  if (L.open_cap > 0x7fffffffull) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: map too large");
+  int rc = fm.d_astar.alloc(ctx, L.bytes);
+  if (rc == SVSDF_OK && !ctx->fstage.h_astar) rc = ctx->fstage.h_astar.alloc(ctx, 1);
   if (rc) return rc;
-  static_assert(sizeof(AstarState) <= 256, "state header");
-  AstarDev &a = ctx->astar;
-  unsigned char *b = ctx->d_astar;
-  a.st = reinterpret_cast<AstarState *>(b);
-  double *d = reinterpret_cast<double *>(b + head);
-  a.g = d; a.f = d + cells; a.yaw = d + 2 * cells;
-  a.okey = d + 3 * cells;
-  a.oseq = reinterpret_cast<unsigned long long *>(d + 3 * cells + cap);
-  a.path_yaw = d + 3 * cells + 2 * cap;
-  int *i4 = reinterpret_cast<int *>(d + 3 * cells + 3 * cap);
-  a.father = i4; a.ocell = i4 + cells; a.path_cell = i4 + cells + cap;
-  a.id = reinterpret_cast<signed char *>(i4 + cells + 2 * cap);
-  a.open_cap = (int)cap;
+  static_assert(sizeof(AstarState) <= lay::kAstarHead, "state header");
+  AstarDev &a = fm.astar;
+  unsigned char *b = fm.d_astar;
+  a.st = lay::at<AstarState>(b, L.st);
+  a.g = lay::at<double>(b, L.g); a.f = lay::at<double>(b, L.f); a.yaw = lay::at<double>(b, L.yaw);
+  a.okey = lay::at<double>(b, L.okey);
+  a.oseq = lay::at<unsigned long long>(b, L.oseq);
+  a.path_yaw = lay::at<double>(b, L.path_yaw);
+  a.father = lay::at<int>(b, L.father); a.ocell = lay::at<int>(b, L.ocell); a.path_cell = lay::at<int>(b, L.path_cell);
+  a.id = lay::at<signed char>(b, L.id);
+  a.open_cap = (int)L.open_cap;
   return SVSDF_OK;
 }
 
@@ -411,144 +400,132 @@ static int astar_axis_index(double p, double bmin, double res, int size) {
   return i;
 }
 
-int svsdf_astar_search(svsdf_ctx *ctx, const double start_xyz[3], const double end_xyz[3], const svsdf_astar_params *params,
+int svsdf_astar_search(svsdf_ctx *group, const double start_xyz[3], const double end_xyz[3], const svsdf_astar_params *params,
                        double *path_xyyaw, int *path_ij, size_t capacity_cells, svsdf_astar_result *result) {
-  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_astar_search: no device context");
-  if (!ctx->subs.empty()) {
-    const int r = svsdf_astar_search(ctx->subs[0], start_xyz, end_xyz, params, path_xyyaw, path_ij, capacity_cells, result);
-    if (r) ctx->err = ctx->subs[0]->err;
-    return r;
-  }
-  if (!ctx->fm_set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: no map (svsdf_frontend_set_map)");
-  if (!start_xyz || !end_xyz || !result) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: null argument");
-  svsdf_astar_params prm;
-  svsdf_astar_params_default(&prm);
-  if (params) {
-    if (params->struct_size != (int)sizeof(svsdf_astar_params))
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: params->struct_size is not sizeof(svsdf_astar_params)");
-    prm = *params;
-  }
-  if (result->struct_size != (int)sizeof(svsdf_astar_result))
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: result->struct_size is not sizeof(svsdf_astar_result)");
-  const FrontMapDev &fm = ctx->fm;
-  {
-    double cy;
-    int ki;
-    if (kernel_bfs(0ull, fm.kernel_count, prm.start_yaw, &cy, &ki) < 0)
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: start_yaw maps to a kernel index outside [0, kernel_count)");
-  }
-  if (prm.slice < 0) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: slice < 0");
-  if (prm.max_expansions < 0) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: max_expansions < 0");
-  for (int d = 0; d < 3; ++d)
-    if (!std::isfinite(start_xyz[d]) || !std::isfinite(end_xyz[d]))
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: start or end not finite");
-  *result = svsdf_astar_result{};
-  result->struct_size = (int)sizeof(svsdf_astar_result);
-  if (!astar_in_map(fm, start_xyz) || !astar_in_map(fm, end_xyz)) {   // front_end_Astar.hpp:249-254
-    result->status = SVSDF_ASTAR_OUT_OF_MAP;
-    return SVSDF_OK;
-  }
-  if (astar_axis_index(start_xyz[2], fm.bmin[2], fm.res, ctx->fm_Z) != 0 || astar_axis_index(end_xyz[2], fm.bmin[2], fm.res, ctx->fm_Z) != 0)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: the search is planar in layer 0; the z index of start or end is not 0");
-  const int slice = prm.slice ? prm.slice : kAstarDefaultSlice;
+  return on_device(group, __func__, [&](svsdf_ctx *ctx) -> int {
+    if (!ctx->fmap.set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: no map (svsdf_frontend_set_map)");
+    if (!start_xyz || !end_xyz || !result) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: null argument");
+    svsdf_astar_params prm;
+    svsdf_astar_params_default(&prm);
+    if (params) {
+      if (params->struct_size != (int)sizeof(svsdf_astar_params))
+        return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: params->struct_size is not sizeof(svsdf_astar_params)");
+      prm = *params;
+    }
+    if (result->struct_size != (int)sizeof(svsdf_astar_result))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: result->struct_size is not sizeof(svsdf_astar_result)");
+    const FrontMapDev &fm = ctx->fmap.dev;
+    {
+      double cy;
+      int ki;
+      if (kernel_bfs(0ull, fm.kernel_count, prm.start_yaw, &cy, &ki) < 0)
+        return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: start_yaw maps to a kernel index outside [0, kernel_count)");
+    }
+    if (prm.slice < 0) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: slice < 0");
+    if (prm.max_expansions < 0) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: max_expansions < 0");
+    for (int d = 0; d < 3; ++d)
+      if (!std::isfinite(start_xyz[d]) || !std::isfinite(end_xyz[d]))
+        return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: start or end not finite");
+    *result = svsdf_astar_result{};
+    result->struct_size = (int)sizeof(svsdf_astar_result);
+    if (!astar_in_map(fm, start_xyz) || !astar_in_map(fm, end_xyz)) {   // front_end_Astar.hpp:249-254
+      result->status = SVSDF_ASTAR_OUT_OF_MAP;
+      return SVSDF_OK;
+    }
+    if (astar_axis_index(start_xyz[2], fm.bmin[2], fm.res, ctx->fmap.Z) != 0 || astar_axis_index(end_xyz[2], fm.bmin[2], fm.res, ctx->fmap.Z) != 0)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: the search is planar in layer 0; the z index of start or end is not 0");
+    const int slice = prm.slice ? prm.slice : kAstarDefaultSlice;
 
-  HIPCHK(hipSetDevice(ctx->device));
-  int rc = astar_alloc(ctx);
-  if (rc) return rc;
-  const AstarDev &a = ctx->astar;
-  const size_t cells = (size_t)fm.X * fm.Y;
-  hipStream_t st = ctx->stream;
-  ctx->astar_searched = false;
-  // AstarPathSearcher::reset (:154-163) + the search's own state
-  AstarState *h = ctx->h_astar;
-  *h = AstarState{};
-  h->status = kAstarRunning;
-  h->si = astar_axis_index(start_xyz[0], fm.bmin[0], fm.res, fm.X);
-  h->sj = astar_axis_index(start_xyz[1], fm.bmin[1], fm.res, fm.Y);
-  h->gi = astar_axis_index(end_xyz[0], fm.bmin[0], fm.res, fm.X);
-  h->gj = astar_axis_index(end_xyz[1], fm.bmin[1], fm.res, fm.Y);
-  h->max_expansions = (unsigned long long)prm.max_expansions;
-  h->start_yaw = prm.start_yaw;
-  h->pushes = 1ull;   // the start node's own openSet.insert (:283); the kernel counts the neighbours'
-  HIPCHK(hipMemsetAsync(a.g, 0, 3 * cells * sizeof(double), st));       // g | f | yaw
-  HIPCHK(hipMemsetAsync(a.father, 0xff, cells * sizeof(int), st));      // -1
-  HIPCHK(hipMemsetAsync(a.id, 0, cells, st));
-  HIPCHK(hipMemcpyAsync(a.st, h, sizeof(AstarState), hipMemcpyHostToDevice, st));
-  unsigned long long launches = 0;
-  do {
-    if (!launch_k_astar(ctx->cfg.shape_id, st, ctx->sp, fm, a, slice))
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: shape not compiled into this library");
-    HIPCHK(hipGetLastError());
-    ++launches;
-    HIPCHK(hipMemcpyAsync(h, a.st, sizeof(AstarState), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-  } while (h->status == kAstarRunning);
-  if (h->status < 0 || h->status > SVSDF_ASTAR_LIMIT)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: internal error: the open set or the path outgrew X * Y + 1 entries");
-  ctx->astar_searched = true;
-  result->status = h->status;
-  result->path_len = h->status == SVSDF_ASTAR_FOUND ? (size_t)h->path_len : 0;
-  result->expansions = h->expansions; result->pushes = h->pushes; result->relaxed_open = h->relaxed_open;
-  result->reopened = h->reopened; result->launches = launches;
-  for (int k = 0; k < 5; ++k) result->stage_counts[k] = h->stage_counts[k];
-  result->g_goal = h->status == SVSDF_ASTAR_FOUND ? h->g_goal : 0.0;
-  const size_t n = result->path_len;
-  if ((path_xyyaw || path_ij) && n) {
-    if (capacity_cells < n)
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: capacity_cells too small (result->path_len cells are needed)");
-    std::vector<int> cell(n);
-    std::vector<double> yaw(n);
-    HIPCHK(hipMemcpyAsync(cell.data(), a.path_cell, n * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(yaw.data(), a.path_yaw, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (size_t k = 0; k < n; ++k) {
-      const int i = cell[k] / fm.Y, j = cell[k] - i * fm.Y;
-      if (path_ij) { path_ij[2 * k] = i; path_ij[2 * k + 1] = j; }
-      if (path_xyyaw) {   // getGridCubeCenter (Gridmap3D.cpp:184-195), coord(2) = yaw (:381)
-        path_xyyaw[3 * k] = (i + 0.5) * fm.res + fm.bmin[0];
-        path_xyyaw[3 * k + 1] = (j + 0.5) * fm.res + fm.bmin[1];
-        path_xyyaw[3 * k + 2] = yaw[k];
+    HIPCHK(hipSetDevice(ctx->device));
+    int rc = astar_alloc(ctx);
+    if (rc) return rc;
+    const AstarDev &a = ctx->fmap.astar;
+    const size_t cells = (size_t)fm.X * fm.Y;
+    hipStream_t st = ctx->stream;
+    ctx->fmap.searched = false;
+    // AstarPathSearcher::reset (:154-163) + the search's own state
+    AstarState *h = ctx->fstage.h_astar;
+    *h = AstarState{};
+    h->status = kAstarRunning;
+    h->si = astar_axis_index(start_xyz[0], fm.bmin[0], fm.res, fm.X);
+    h->sj = astar_axis_index(start_xyz[1], fm.bmin[1], fm.res, fm.Y);
+    h->gi = astar_axis_index(end_xyz[0], fm.bmin[0], fm.res, fm.X);
+    h->gj = astar_axis_index(end_xyz[1], fm.bmin[1], fm.res, fm.Y);
+    h->max_expansions = (unsigned long long)prm.max_expansions;
+    h->start_yaw = prm.start_yaw;
+    h->pushes = 1ull;   // the start node's own openSet.insert (:283); the kernel counts the neighbours'
+    HIPCHK(hipMemsetAsync(a.g, 0, 3 * cells * sizeof(double), st));       // g | f | yaw
+    HIPCHK(hipMemsetAsync(a.father, 0xff, cells * sizeof(int), st));      // -1
+    HIPCHK(hipMemsetAsync(a.id, 0, cells, st));
+    HIPCHK(hipMemcpyAsync(a.st, h, sizeof(AstarState), hipMemcpyHostToDevice, st));
+    unsigned long long launches = 0;
+    do {
+      if (!launch_k_astar(ctx->cfg.shape_id, st, ctx->sp, fm, a, slice))
+        return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: shape not compiled into this library");
+      HIPCHK(hipGetLastError());
+      ++launches;
+      HIPCHK(hipMemcpyAsync(h, a.st, sizeof(AstarState), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+    } while (h->status == kAstarRunning);
+    if (h->status < 0 || h->status > SVSDF_ASTAR_LIMIT)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: internal error: the open set or the path outgrew X * Y + 1 entries");
+    ctx->fmap.searched = true;
+    result->status = h->status;
+    result->path_len = h->status == SVSDF_ASTAR_FOUND ? (size_t)h->path_len : 0;
+    result->expansions = h->expansions; result->pushes = h->pushes; result->relaxed_open = h->relaxed_open;
+    result->reopened = h->reopened; result->launches = launches;
+    for (int k = 0; k < 5; ++k) result->stage_counts[k] = h->stage_counts[k];
+    result->g_goal = h->status == SVSDF_ASTAR_FOUND ? h->g_goal : 0.0;
+    const size_t n = result->path_len;
+    if ((path_xyyaw || path_ij) && n) {
+      if (capacity_cells < n)
+        return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_search: capacity_cells too small (result->path_len cells are needed)");
+      std::vector<int> cell(n);
+      std::vector<double> yaw(n);
+      HIPCHK(hipMemcpyAsync(cell.data(), a.path_cell, n * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(yaw.data(), a.path_yaw, n * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      for (size_t k = 0; k < n; ++k) {
+        const int i = cell[k] / fm.Y, j = cell[k] - i * fm.Y;
+        if (path_ij) { path_ij[2 * k] = i; path_ij[2 * k + 1] = j; }
+        if (path_xyyaw) {   // getGridCubeCenter (Gridmap3D.cpp:184-195), coord(2) = yaw (:381)
+          path_xyyaw[3 * k] = (i + 0.5) * fm.res + fm.bmin[0];
+          path_xyyaw[3 * k + 1] = (j + 0.5) * fm.res + fm.bmin[1];
+          path_xyyaw[3 * k + 2] = yaw[k];
+        }
       }
     }
-  }
-  return SVSDF_OK;
+    return SVSDF_OK;
+  });
 }
 
-int svsdf_astar_nodes(const svsdf_ctx *cctx, signed char *id, double *g, double *f, double *yaw, int *father_cell,
+int svsdf_astar_nodes(const svsdf_ctx *group, signed char *id, double *g, double *f, double *yaw, int *father_cell,
                       size_t capacity, int dims2[2]) {
-  svsdf_ctx *ctx = const_cast<svsdf_ctx *>(cctx);   // (the error string is the only thing written)
-  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_astar_nodes: no device context");
-  if (!ctx->subs.empty()) {
-    const int r = svsdf_astar_nodes(ctx->subs[0], id, g, f, yaw, father_cell, capacity, dims2);
-    if (r) ctx->err = ctx->subs[0]->err;
-    return r;
-  }
-  if (!ctx->fm_set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_nodes: no map (svsdf_frontend_set_map)");
-  if (dims2) { dims2[0] = ctx->fm.X; dims2[1] = ctx->fm.Y; }
-  if (!id && !g && !f && !yaw && !father_cell) return SVSDF_OK;
-  if (!ctx->astar_searched) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_nodes: no search on this map yet (svsdf_astar_search)");
-  const size_t n = (size_t)ctx->fm.X * ctx->fm.Y;
-  if (capacity < n) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_nodes: capacity too small (query with all pointers NULL first)");
-  const AstarDev &a = ctx->astar;
-  hipStream_t st = ctx->stream;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (id) HIPCHK(hipMemcpyAsync(id, a.id, n, hipMemcpyDeviceToHost, st));
-  if (g) HIPCHK(hipMemcpyAsync(g, a.g, n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (f) HIPCHK(hipMemcpyAsync(f, a.f, n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (yaw) HIPCHK(hipMemcpyAsync(yaw, a.yaw, n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (father_cell) HIPCHK(hipMemcpyAsync(father_cell, a.father, n * sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return SVSDF_OK;
+  // (const: the error string is the only thing written)
+  return on_device(const_cast<svsdf_ctx *>(group), __func__, [&](svsdf_ctx *ctx) -> int {
+    const FrontMap &fm = ctx->fmap;
+    if (!fm.set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_nodes: no map (svsdf_frontend_set_map)");
+    if (dims2) { dims2[0] = fm.dev.X; dims2[1] = fm.dev.Y; }
+    if (!id && !g && !f && !yaw && !father_cell) return SVSDF_OK;
+    if (!fm.searched) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_nodes: no search on this map yet (svsdf_astar_search)");
+    const size_t n = (size_t)fm.dev.X * fm.dev.Y;
+    if (capacity < n) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_astar_nodes: capacity too small (query with all pointers NULL first)");
+    const AstarDev &a = fm.astar;
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipSetDevice(ctx->device));
+    if (id) HIPCHK(hipMemcpyAsync(id, a.id, n, hipMemcpyDeviceToHost, st));
+    if (g) HIPCHK(hipMemcpyAsync(g, a.g, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (f) HIPCHK(hipMemcpyAsync(f, a.f, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (yaw) HIPCHK(hipMemcpyAsync(yaw, a.yaw, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (father_cell) HIPCHK(hipMemcpyAsync(father_cell, a.father, n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return SVSDF_OK;
+  });
 }
 
 // ---- mesh shapes (host) ------------------------------------------------------------------------------
 static int outline_out(const std::vector<double> &xy, double *xy_out, size_t capacity_verts, size_t *count) {
-  *count = xy.size() / 2;
-  if (xy_out) {
-    if (capacity_verts < *count) return SVSDF_ERR_INVALID;
-    std::copy(xy.begin(), xy.end(), xy_out);
-  }
-  return SVSDF_OK;
+  return deliver(Out<double>{xy, 2, xy_out, capacity_verts, count}) ? SVSDF_OK : SVSDF_ERR_INVALID;
 }
 int svsdf_mesh_outline(const double *V, size_t nv, const int *F, size_t nf, double z0, double *xy_out,
                        size_t capacity_verts, size_t *count, int *loops) {
@@ -559,15 +536,8 @@ int svsdf_mesh_outline(const double *V, size_t nv, const int *F, size_t nf, doub
 }
 static int section_out(const std::vector<double> &xy, const std::vector<int> &sizes, double *xy_out, size_t capacity_verts,
                        size_t *n_verts, int *loop_sizes, size_t capacity_loops, size_t *n_loops) {
-  *n_verts = xy.size() / 2;
-  *n_loops = sizes.size();
-  if ((xy_out == nullptr) != (loop_sizes == nullptr)) return SVSDF_ERR_INVALID;
-  if (xy_out) {
-    if (capacity_verts < *n_verts || capacity_loops < *n_loops) return SVSDF_ERR_INVALID;
-    std::copy(xy.begin(), xy.end(), xy_out);
-    std::copy(sizes.begin(), sizes.end(), loop_sizes);
-  }
-  return SVSDF_OK;
+  const bool ok = deliver(Out<double>{xy, 2, xy_out, capacity_verts, n_verts}, Out<int>{sizes, 1, loop_sizes, capacity_loops, n_loops});
+  return ok && (xy_out == nullptr) == (loop_sizes == nullptr) ? SVSDF_OK : SVSDF_ERR_INVALID;   // both outputs, or neither
 }
 int svsdf_mesh_section(const double *V, size_t nv, const int *F, size_t nf, double z0, double *xy_out, size_t capacity_verts,
                        size_t *n_verts, int *loop_sizes, size_t capacity_loops, size_t *n_loops) {
@@ -607,7 +577,7 @@ int svsdf_swept_outline(svsdf_ctx *ctx, int N, const double *coeffs, const doubl
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_swept_outline: N, cell or margin out of range");
   if ((xy_out == nullptr) != (loop_sizes == nullptr))
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_swept_outline: xy_out and loop_sizes must both be given (fill) or both be NULL (size query)");
-  const svsdf_ctx *base = ctx->subs.empty() ? ctx : ctx->subs[0];
+  const svsdf_ctx *base = leaf_of(ctx);
   if (base->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "host-only context: no device entry points");
   // the size query and the fill that follows it carry the same arguments: the second call copies the first one's result
   std::vector<double> key;
@@ -615,20 +585,15 @@ int svsdf_swept_outline(svsdf_ctx *ctx, int N, const double *coeffs, const doubl
   key.push_back((double)N); key.push_back(cell); key.push_back(margin);
   key.insert(key.end(), coeffs, coeffs + 18 * (size_t)N);
   key.insert(key.end(), T, T + N);
-  auto deliver = [&](const std::vector<double> &xy, const std::vector<int> &loops, const svsdf_outline_stats &st) -> int {
-    *n_verts = xy.size() / 2;
-    *n_loops = loops.size();
-    if (stats_out) *stats_out = st;
-    if (xy_out && loop_sizes) {
-      if (capacity_verts < xy.size() / 2 || capacity_loops < loops.size())
-        return fail(ctx, SVSDF_ERR_INVALID, "svsdf_swept_outline: output capacity too small (query with xy_out = NULL first)");
-      std::copy(xy.begin(), xy.end(), xy_out);
-      std::copy(loops.begin(), loops.end(), loop_sizes);
-    }
+  OutlineCache &ol = ctx->outline;
+  auto deliver_cached = [&]() -> int {
+    if (stats_out) *stats_out = ol.stats;
+    if (!deliver(Out<double>{ol.xy, 2, xy_out, capacity_verts, n_verts}, Out<int>{ol.loops, 1, loop_sizes, capacity_loops, n_loops}))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_swept_outline: output capacity too small (query with xy_out = NULL first)");
     return SVSDF_OK;
   };
-  if (ctx->ol_valid && ctx->ol_key.size() == key.size() && std::memcmp(ctx->ol_key.data(), key.data(), key.size() * sizeof(double)) == 0)
-    return deliver(ctx->ol_xy, ctx->ol_loops, ctx->ol_stats);
+  if (ol.valid && ol.key.size() == key.size() && std::memcmp(ol.key.data(), key.data(), key.size() * sizeof(double)) == 0)
+    return deliver_cached();
   // bounding box of the path (body origin), grown by the shape's bound radius: the swept volume lies inside
   double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
   for (int i = 0; i < N; ++i) {
@@ -691,15 +656,14 @@ int svsdf_swept_outline(svsdf_ctx *ctx, int N, const double *coeffs, const doubl
   const std::string tmp_err = rc ? svsdf_last_error_string(tmp) : "";
   svsdf_destroy(tmp);
   if (rc) return fail(ctx, rc > 0 ? rc : SVSDF_ERR_INVALID, "svsdf_swept_outline: evaluation failed: " + tmp_err);
-  svsdf_outline_stats so{};
-  so.nodes_evaluated = st.nodes_evaluated; so.dense_nodes = st.dense_nodes;
-  so.cells_marched = st.cells_marched; so.batches = st.batches; so.open_chains = st.open_chains;
-  ctx->ol_key.swap(key);
-  ctx->ol_xy = xy;
-  ctx->ol_loops = loops;
-  ctx->ol_stats = so;
-  ctx->ol_valid = true;
-  return deliver(ctx->ol_xy, ctx->ol_loops, ctx->ol_stats);
+  ol.stats = svsdf_outline_stats{};
+  ol.stats.nodes_evaluated = st.nodes_evaluated; ol.stats.dense_nodes = st.dense_nodes;
+  ol.stats.cells_marched = st.cells_marched; ol.stats.batches = st.batches; ol.stats.open_chains = st.open_chains;
+  ol.key.swap(key);
+  ol.xy = xy;
+  ol.loops = loops;
+  ol.valid = true;
+  return deliver_cached();
 }
 
 int svsdf_outline_extrude(const double *xy, const int *loop_sizes, size_t n_loops, double z0, double z1, int caps,
@@ -713,13 +677,7 @@ int svsdf_outline_extrude(const double *xy, const int *loop_sizes, size_t n_loop
   std::vector<double> V;
   std::vector<int> F;
   svsdf_host::extrude_outline(xy, loop_sizes, n_loops, z0, z1, caps != 0, V, F);
-  *n_verts = V.size() / 3;
-  *n_tris = F.size() / 3;
-  if (!V_out || !F_out) return SVSDF_OK;
-  if (capacity_verts < V.size() / 3 || capacity_tris < F.size() / 3) return SVSDF_ERR_INVALID;
-  std::copy(V.begin(), V.end(), V_out);
-  std::copy(F.begin(), F.end(), F_out);
-  return SVSDF_OK;
+  return deliver(Out<double>{V, 3, V_out, capacity_verts, n_verts}, Out<int>{F, 3, F_out, capacity_tris, n_tris}) ? SVSDF_OK : SVSDF_ERR_INVALID;
 }
 
 }  // extern "C"

@@ -201,7 +201,6 @@ def lib():
     L.svsdf_debug_sqrt_mismatches.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_int]
     L.svsdf_lbfgs_params_default.argtypes = [C.POINTER(LbfgsParams)]
     L.svsdf_lbfgs_params_default.restype = None
-    _ip = C.POINTER(C.c_int)
     L.svsdf_lbfgs_minimize.argtypes = [C.c_int, _dp, EVALUATE_T, C.c_void_p, PROGRESS_T, C.c_void_p,
                                        C.POINTER(LbfgsParams), _dp, _ip, _ip]
     L.svsdf_optimize_traj.argtypes = [C.c_void_p, _dp, C.c_int, C.POINTER(LbfgsParams), PROGRESS_T, C.c_void_p,
@@ -225,7 +224,18 @@ def lib():
     L.svsdf_swept_outline.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, C.c_size_t,
                                       C.POINTER(C.c_size_t), _ip, C.c_size_t, C.POINTER(C.c_size_t),
                                       C.POINTER(OutlineStats)]
-    if hasattr(L, "svsdf_get_plan"):   # (absent only from A/B libraries built from older commits, tools/exp_variants.py)
+    L.svsdf_outline_extrude.argtypes = [_dp, _ip, C.c_size_t, C.c_double, C.c_double, C.c_int, _dp, C.c_size_t,
+                                        C.POINTER(C.c_size_t), _ip, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "svsdf_mesh_section"):   # (the guards: absent only from A/B libraries built from older commits, tools/build_ref_variant.sh)
+        L.svsdf_mesh_section.argtypes = [_dp, C.c_size_t, _ip, C.c_size_t, C.c_double, _dp, C.c_size_t, C.POINTER(C.c_size_t), _ip,
+                                         C.c_size_t, C.POINTER(C.c_size_t)]
+        L.svsdf_mesh_section_obj.argtypes = [C.c_char_p, C.c_double, _dp, C.c_size_t, C.POINTER(C.c_size_t), _ip, C.c_size_t,
+                                             C.POINTER(C.c_size_t)]
+    if hasattr(L, "svsdf_debug_sdf_at"):
+        L.svsdf_debug_sdf_at.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_size_t, _dp, _dp, _dp]
+    if hasattr(L, "svsdf_shape_selfcheck"):
+        L.svsdf_shape_selfcheck.argtypes = [C.c_void_p, _dp]
+    if hasattr(L, "svsdf_get_plan"):
         L.svsdf_get_plan.argtypes = [C.c_void_p, C.POINTER(Plan)]
         L.svsdf_set_plan.argtypes = [C.c_void_p, C.POINTER(Plan)]
         L.svsdf_set_combine.argtypes = [C.c_void_p, C.c_int]
@@ -251,6 +261,11 @@ def _f64(a):
 def _colmajor(m):
     """(rows, cols) array -> flat column-major copy (Eigen's default storage)."""
     return np.asfortranarray(_f64(m)).ravel(order="F").copy()
+
+
+def _rows(cm, N):
+    """flat column-major 3 x 6N coefficients (what the library takes and returns; _colmajor of (6N, 3)) -> (6N, 3)."""
+    return cm.reshape(3, 6 * N).T.copy()
 
 
 def kernel_bfs(mask, kernel_count, father_yaw):
@@ -284,7 +299,7 @@ def minco_coeffs(head_state, tail_state, inPs, T):
     rc = lib().svsdf_minco_coeffs(_p(_colmajor(head_state)), _p(_colmajor(tail_state)), N, _p(q), _p(T), _p(out))
     if rc:
         raise SvsdfError(f"svsdf_minco_coeffs failed: {rc}")
-    return out.reshape(3, 6 * N).T.copy()
+    return _rows(out, N)
 
 
 def mesh_outline(V, F, z0=0.0):
@@ -293,12 +308,11 @@ def mesh_outline(V, F, z0=0.0):
     V = _f64(V).reshape(-1, 3)
     F = np.ascontiguousarray(F, dtype=np.int32).reshape(-1, 3)
     n, loops = C.c_size_t(), C.c_int()
-    ip = C.POINTER(C.c_int)
-    rc = lib().svsdf_mesh_outline(_p(V), len(V), F.ctypes.data_as(ip), len(F), float(z0), None, 0, C.byref(n), C.byref(loops))
+    rc = lib().svsdf_mesh_outline(_p(V), len(V), F.ctypes.data_as(_ip), len(F), float(z0), None, 0, C.byref(n), C.byref(loops))
     if rc:
         raise SvsdfError(f"svsdf_mesh_outline failed: {rc}")
     xy = np.zeros((n.value, 2))
-    lib().svsdf_mesh_outline(_p(V), len(V), F.ctypes.data_as(ip), len(F), float(z0), _p(xy), n.value, C.byref(n), C.byref(loops))
+    lib().svsdf_mesh_outline(_p(V), len(V), F.ctypes.data_as(_ip), len(F), float(z0), _p(xy), n.value, C.byref(n), C.byref(loops))
     return xy, loops.value
 
 
@@ -309,16 +323,13 @@ def mesh_section(V, F, z0=0.0):
     V = _f64(V).reshape(-1, 3)
     F = np.ascontiguousarray(F, dtype=np.int32).reshape(-1, 3)
     n, nl = C.c_size_t(), C.c_size_t()
-    ip = C.POINTER(C.c_int)
-    L.svsdf_mesh_section.argtypes = [_dp, C.c_size_t, ip, C.c_size_t, C.c_double, _dp, C.c_size_t, C.POINTER(C.c_size_t), ip,
-                                     C.c_size_t, C.POINTER(C.c_size_t)]
-    rc = L.svsdf_mesh_section(_p(V), len(V), F.ctypes.data_as(ip), len(F), float(z0), None, 0, C.byref(n), None, 0, C.byref(nl))
+    rc = L.svsdf_mesh_section(_p(V), len(V), F.ctypes.data_as(_ip), len(F), float(z0), None, 0, C.byref(n), None, 0, C.byref(nl))
     if rc:
         raise SvsdfError("svsdf_mesh_section failed: " + L.svsdf_last_error_string(None).decode())
     xy = np.zeros((n.value, 2))
     sizes = np.zeros(nl.value, dtype=np.int32)
-    rc = L.svsdf_mesh_section(_p(V), len(V), F.ctypes.data_as(ip), len(F), float(z0), _p(xy), n.value, C.byref(n),
-                              sizes.ctypes.data_as(ip), nl.value, C.byref(nl))
+    rc = L.svsdf_mesh_section(_p(V), len(V), F.ctypes.data_as(_ip), len(F), float(z0), _p(xy), n.value, C.byref(n),
+                              sizes.ctypes.data_as(_ip), nl.value, C.byref(nl))
     if rc:
         raise SvsdfError("svsdf_mesh_section failed: " + L.svsdf_last_error_string(None).decode())
     return xy, [int(v) for v in sizes]
@@ -328,16 +339,13 @@ def mesh_section_obj(path, z0=0.0):
     """The same for a Wavefront .obj file (svsdf_mesh_section_obj)."""
     L = lib()
     n, nl = C.c_size_t(), C.c_size_t()
-    ip = C.POINTER(C.c_int)
-    L.svsdf_mesh_section_obj.argtypes = [C.c_char_p, C.c_double, _dp, C.c_size_t, C.POINTER(C.c_size_t), ip, C.c_size_t,
-                                         C.POINTER(C.c_size_t)]
     path = os.fspath(path)
     rc = L.svsdf_mesh_section_obj(path.encode(), float(z0), None, 0, C.byref(n), None, 0, C.byref(nl))
     if rc:
         raise SvsdfError("svsdf_mesh_section_obj failed: " + L.svsdf_last_error_string(None).decode())
     xy = np.zeros((n.value, 2))
     sizes = np.zeros(nl.value, dtype=np.int32)
-    rc = L.svsdf_mesh_section_obj(path.encode(), float(z0), _p(xy), n.value, C.byref(n), sizes.ctypes.data_as(ip), nl.value,
+    rc = L.svsdf_mesh_section_obj(path.encode(), float(z0), _p(xy), n.value, C.byref(n), sizes.ctypes.data_as(_ip), nl.value,
                                   C.byref(nl))
     if rc:
         raise SvsdfError("svsdf_mesh_section_obj failed: " + L.svsdf_last_error_string(None).decode())
@@ -362,8 +370,6 @@ def outline_extrude(loops, z0=-0.5, z1=0.5, caps=True):
     sizes = np.ascontiguousarray([len(lp) for lp in loops], dtype=np.int32)
     nv, nf = C.c_size_t(), C.c_size_t()
     L = lib()
-    L.svsdf_outline_extrude.argtypes = [_dp, _ip, C.c_size_t, C.c_double, C.c_double, C.c_int, _dp, C.c_size_t,
-                                        C.POINTER(C.c_size_t), _ip, C.c_size_t, C.POINTER(C.c_size_t)]
     rc = L.svsdf_outline_extrude(_p(xy), sizes.ctypes.data_as(_ip), len(sizes), z0, z1, int(bool(caps)), None, 0,
                                  C.byref(nv), None, 0, C.byref(nf))
     if rc:
@@ -591,7 +597,7 @@ class SvsdfContext:
         gT = np.zeros(N) if gradT0 is None else _f64(gradT0).copy()
         gC = np.zeros(18 * N) if gradC0 is None else _colmajor(gradC0)
         self._chk(self.L.svsdf_eval_penalty(self.ctx, N, _p(cm), _p(T), C.byref(cost), _p(gT), _p(gC)), "svsdf_eval_penalty")
-        return cost.value, gT, gC.reshape(3, 6 * N).T.copy()
+        return cost.value, gT, _rows(gC, N)
 
     def eval_penalty_partial(self, coeffs, T):
         """Runs the device pipeline; returns (device pointer, length) of [cost, gradC, gradT]."""
@@ -608,7 +614,7 @@ class SvsdfContext:
         gT = np.zeros(N) if gradT0 is None else _f64(gradT0).copy()
         gC = np.zeros(18 * N) if gradC0 is None else _colmajor(gradC0)
         self._chk(self.L.svsdf_accumulate_partial(self.ctx, N, _p(partial), C.byref(cost), _p(gT), _p(gC)), "svsdf_accumulate_partial")
-        return cost.value, gT, gC.reshape(3, 6 * N).T.copy()
+        return cost.value, gT, _rows(gC, N)
 
     # ---- full callback ----
     def lmbm_evaluate(self, x):
@@ -636,7 +642,7 @@ class SvsdfContext:
         N = (len(x) + 3) // 4
         cm, T = np.zeros(18 * N), np.zeros(N)
         self._chk(self.L.svsdf_lmbm_prepare(self.ctx, _p(x), len(x), _p(cm), _p(T)), "svsdf_lmbm_prepare")
-        return cm.reshape(3, 6 * N).T.copy(), T
+        return _rows(cm, N), T
 
     def lmbm_finish(self, partial, n):
         partial = _f64(partial)
@@ -811,7 +817,6 @@ class SvsdfContext:
         xy = _f64(points_xy).reshape(-1, 2).copy()
         tt = _f64(t).ravel().copy()
         out = np.zeros((len(tt), 8))
-        self.L.svsdf_debug_sdf_at.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_size_t, _dp, _dp, _dp]
         self._chk(self.L.svsdf_debug_sdf_at(self.ctx, len(T), _p(cm), _p(T), len(tt), _p(xy), _p(tt), _p(out)), "svsdf_debug_sdf_at")
         return out
 
@@ -832,7 +837,6 @@ class SvsdfContext:
     def shape_selfcheck(self):
         """(R analytic, R sampled, Lipschitz excess: 0 = the shape SDF passed the 1-Lipschitz self-check)."""
         o = np.zeros(3)
-        self.L.svsdf_shape_selfcheck.argtypes = [C.c_void_p, _dp]
         self._chk(self.L.svsdf_shape_selfcheck(self.ctx, _p(o)), "svsdf_shape_selfcheck")
         return float(o[0]), float(o[1]), float(o[2])
 

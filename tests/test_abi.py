@@ -20,6 +20,17 @@ def test_exports_every_declared_symbol(built):
     assert declared == set(binding.EXPORTS), declared ^ set(binding.EXPORTS)
 
 
+def test_every_prototype_is_declared_at_load(built):
+    """binding.lib() declares the argument types of every exported entry point itself: none is left to the first call of
+    a method (ctypes would pass a Python int as a C int, and truncate a size_t or a pointer, until then)."""
+    from svsdf_amd import binding
+    L = binding.lib()
+    exported = [n for n in binding.EXPORTS if hasattr(L, n)]
+    assert len(exported) == len(binding.EXPORTS)          # the library under test exports them all (test above)
+    missing = [n for n in exported if getattr(L, n).argtypes is None]
+    assert not missing, missing
+
+
 def test_shape_registry_lookup(built):
     import svsdf_amd
     assert svsdf_amd.shape_id_from_inputdata("shapes/star.obj") == svsdf_amd.SHAPE_ID["star"]

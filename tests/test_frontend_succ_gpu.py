@@ -374,3 +374,70 @@ def test_plumbing(built):
     np.testing.assert_array_equal(multi.yaw_free(), case["free"])
     okm, cym, stm = multi.astar_successors(ij, yw)
     assert okm.tobytes() == okb.tobytes() and cym.tobytes() == cyb.tobytes() and stm.tobytes() == stb.tobytes()
+
+
+# ---------------------------------------------------------------- entries reached through a group; the chunk loop
+@pytest.fixture(scope="module")
+def small_map(built):
+    """The 13 x 70 random map of test_plumbing (kernels 9 / 8 on it)."""
+    import svsdf_amd
+    g = layout("random", 13, 70, seed=7)
+    return g, svsdf_amd.OccupancyMap(cloud_of(g, 1.0), resolution=1.0, sta_threshold=2)
+
+
+def test_entries_through_a_group(ctxs, small_map):
+    """svsdf_check_sub_sw_collision and svsdf_shape_kernels on a multi-device context run on its first stripe: the same
+    bytes as a single-device context.  An entry that fails there hands the stripe's error text to the group."""
+    import svsdf_amd
+    g, om = small_map
+    single = ctxs("star")
+    multi = svsdf_amd.SvsdfContext(shape="star", devices=[0, 0])
+    with pytest.raises(svsdf_amd.SvsdfError, match="no map"):      # before any frontend_set_map on the group
+        multi.astar_search([0.5, 0.5, 0.5], [12.5, 69.5, 0.5])
+    # three edges with 0, 1 and 70 obstacle points: the occupied cells' centres, nearest to the father first
+    ii, jj = np.nonzero(g)
+    cen = np.column_stack([ii + 0.5, jj + 0.5])
+    father = np.array([6.5, 30.5, 0.0])
+    near = cen[np.argsort(np.hypot(cen[:, 0] - father[0], cen[:, 1] - father[1]), kind="stable")]
+    assert len(near) >= 70
+    fs = np.tile(father, (3, 1))
+    cs = np.array([[7.5, 31.5, 0.4], [7.5, 30.5, -0.8], [5.5, 29.5, 2.0]])
+    pts = [np.zeros((0, 2)), near[-1:], near[:70]]
+    want = single.check_sub_sw_collision(fs, cs, pts)
+    got = multi.check_sub_sw_collision(fs, cs, pts)
+    assert got.dtype == want.dtype and got.tobytes() == want.tobytes()
+    assert want[0]                                                 # no point: nothing to collide with
+    ms, bs, ys, ns = single.shape_kernels(9, 8, 1.0, 0.5)
+    mm, bm, ym, nm = multi.shape_kernels(9, 8, 1.0, 0.5)
+    assert mm.tobytes() == ms.tobytes() and bm.tobytes() == bs.tobytes() and ym.tobytes() == ys.tobytes() and nm == ns
+    assert ms.any() and not ms.all()
+    multi.frontend_set_map(om, 9, 8, MARGIN)
+    assert multi.astar_search([0.5, 0.5, 0.5], [12.5, 69.5, 0.5])["status"] in ("FOUND", "EXHAUSTED")
+    multi.close()
+
+
+def test_successors_chunk_loop(ctxs, small_map):
+    """More than 2^18 parents in one call go to the device in chunks of 2^18: the same bytes as the chunks sent as calls
+    of their own, and as the parents at both sides of the boundary sent alone."""
+    g, om = small_map
+    ctx = ctxs("star")
+    ctx.frontend_set_map(om, 9, 8, MARGIN)
+    chunk = 1 << 18
+    n = chunk + 3
+    free = np.argwhere(~g).astype(np.int32)
+    reps = -(-n // len(free))
+    ij = np.tile(free, (reps, 1))[:n]
+    hy = handout_yaws(8)
+    yw = np.array([hy[k % 8] for k in range(5)] * (n // 5 + 1))[:n]          # period 5 against the cells' period
+    ok, cy, st = ctx.astar_successors(ij, yw)
+    assert ok.shape == (n, 9) and cy.shape == (n, 9) and st.shape == (n, 9)
+    ok0, cy0, st0 = ctx.astar_successors(ij[:chunk], yw[:chunk])
+    ok1, cy1, st1 = ctx.astar_successors(ij[chunk:], yw[chunk:])
+    assert ok.tobytes() == ok0.tobytes() + ok1.tobytes()
+    assert cy.tobytes() == cy0.tobytes() + cy1.tobytes()
+    assert st.tobytes() == st0.tobytes() + st1.tobytes()
+    for p in (0, chunk - 1, chunk, chunk + 2):
+        okp, cyp, stp = ctx.astar_successors(ij[p:p + 1], yw[p:p + 1])
+        assert okp.tobytes() == ok[p:p + 1].tobytes() and cyp.tobytes() == cy[p:p + 1].tobytes() \
+            and stp.tobytes() == st[p:p + 1].tobytes()
+    print("stages 0..4:", np.bincount(st.ravel(), minlength=5).tolist())
