@@ -320,10 +320,11 @@ static double sdf_arc(const orc_shape *s, double px, double py) {
 }
 
 /* Polygon: SHP:1370-1401 (edge helpers), SHP:1448-1476 (getonlySDF).  NB: no trans/Rotate. */
-static int poly_cross_ray(double sx, double sy, double ex, double ey, double qx, double qy) {
+static double dev_atan2(double y, double x);
+static int poly_cross_ray(double sx, double sy, double ex, double ey, double qx, double qy, int dev) {
   double s2x = sx - qx, s2y = sy - qy, e2x = ex - qx, e2y = ey - qy;
-  double theta_s = atan2(s2y, s2x);
-  double theta_e = atan2(e2y, e2x);
+  double theta_s = dev ? dev_atan2(s2y, s2x) : atan2(s2y, s2x);
+  double theta_e = dev ? dev_atan2(e2y, e2x) : atan2(e2y, e2x);
   theta_s = (theta_s < 0.0) ? (theta_s + 2 * ORC_PI) : theta_s;
   theta_e = (theta_e < 0.0) ? (theta_e + 2 * ORC_PI) : theta_e;
   double d1 = fabs(theta_s - theta_e);
@@ -347,7 +348,7 @@ static double sdf_polygon(const orc_shape *s, double x, double y, double *cminx,
     int j = s->next[i];   /* (i + 1) % nverts for the reference's single chain */
     double dis = poly_dis2seg(s->vx[i], s->vy[i], s->vx[j], s->vy[j], x, y, &cx, &cy);
     if (dis < dis_min) { dis_min = dis; mx = cx; my = cy; }
-    if (poly_cross_ray(s->vx[i], s->vy[i], s->vx[j], s->vy[j], x, y)) rs++;
+    if (poly_cross_ray(s->vx[i], s->vy[i], s->vx[j], s->vy[j], x, y, s->dev_atan2)) rs++;
   }
   if (cminx) { *cminx = mx; *cminy = my; }
   return (rs % 2 == 0) ? dis_min : -dis_min;
@@ -632,16 +633,19 @@ static inline double trig_sin(const orc_ctx *ctx, double a) {
 void orc_set_trig_perturb(orc_ctx *ctx, unsigned long long seed) {
   /* libm trig moved by <= 1 ulp (seeded), the reference's piece location: a third oracle for the sensitivity bracket */
   ctx->trig_mode = 2;
+  ctx->shape.dev_atan2 = 0;
   ctx->trig_seed = seed * 0x9e3779b97f4a7c15ULL + 0x632be59bd9b4e019ULL;
   ctx->traj.cum_locate = 0;
 }
 void orc_set_modes(orc_ctx *ctx, int trig_mode, int cum_locate) {
   /* the two diagnostic switches separately: device-library trig (1) and cumulative piece location (1) */
   ctx->trig_mode = trig_mode ? 1 : 0;
+  ctx->shape.dev_atan2 = ctx->trig_mode;
   ctx->traj.cum_locate = cum_locate ? 1 : 0;
 }
 void orc_set_trig_mode(orc_ctx *ctx, int mode) {
   ctx->trig_mode = mode ? 1 : 0;
+  ctx->shape.dev_atan2 = ctx->trig_mode;
   ctx->traj.cum_locate = ctx->trig_mode;
 }
 

@@ -76,6 +76,10 @@ typedef struct orc_shape {
    * solids: BASELINE config 5 says "arbitrary .obj mesh") is the same loop over the union of the loops' edges:
    * orc_shape_set_loops closes every loop on its own first vertex. */
   int next[ORC_MAX_POLY_VERTS];
+  /* Polygon: 1 = the two atan2 calls of isCrossRayOnXDir by the device library's algorithm (orc_set_modes / orc_set_trig_mode,
+   * the device-arithmetic mode), 0 = libm (the oracle of record).  The two differ only where |theta_s - theta_e| is within
+   * rounding of pi: a query within about an ulp of an edge, where the value is +-1e-16. */
+  int dev_atan2;
 } orc_shape;
 
 typedef struct orc_traj {
