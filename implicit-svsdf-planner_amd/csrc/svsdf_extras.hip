@@ -24,6 +24,12 @@ static std::vector<double> shape_kernel_yaws(int kernel_count, int *loop_count) 
   return yaws;
 }
 
+// A Polygon context has yaw kernels -- and with them the resident map, successors and search -- only when it was created
+// with SVSDF_FLAG_POLYGON_YAW_KERNELS (svsdf_c.h: the reference's stated intent, shape_sdf_rot<kPolygon>)
+static bool polygon_refused(const svsdf_ctx *ctx) {
+  return ctx->cfg.shape_id == SVSDF_SHAPE_Polygon && !(ctx->cfg.flags & SVSDF_FLAG_POLYGON_YAW_KERNELS);
+}
+
 // The byte kernels of `yaws` (BasicShape::initShape's loop, SHP:400-428) into the caller's d_map, kernel_size^2 bytes per yaw:
 // the yaw table's upload, then k_shape_kernels.  `what` names the caller in a HIP error.  `uncompiled`: the caller's error for a
 // shape that is not compiled into the library, null to go on without one.  `then_upload` (optional) queues the caller's own
@@ -131,7 +137,7 @@ int svsdf_shape_kernels(svsdf_ctx *group, int kernel_size, int kernel_count, dou
   return on_device(group, __func__, [&](svsdf_ctx *ctx) -> int {
     if (kernel_size <= 0 || kernel_count <= 0 || kernel_size > 4096 || kernel_count > 65536 || !map_out)
       return fail(ctx, SVSDF_ERR_INVALID, "svsdf_shape_kernels: bad argument");
-    if (ctx->cfg.shape_id == SVSDF_SHAPE_Polygon)
+    if (polygon_refused(ctx))
       return fail(ctx, SVSDF_ERR_INVALID,
                   "svsdf_shape_kernels: Polygon has no getonlySDF(pos_rel, Matrix3d) in the reference (Shape.hpp:1477)");
     int ind = 0;
@@ -207,7 +213,7 @@ int svsdf_pcd_read_ascii(const char *path, float *xyz, size_t capacity, size_t *
 int svsdf_frontend_set_map(svsdf_ctx *group, const svsdf_map *map, int kernel_size, int kernel_count, double safemargin) {
   return on_device(group, __func__, [&](svsdf_ctx *ctx) -> int {
     if (!map) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: null map");
-    if (ctx->cfg.shape_id == SVSDF_SHAPE_Polygon)
+    if (polygon_refused(ctx))
       return fail(ctx, SVSDF_ERR_INVALID,
                   "svsdf_frontend_set_map: Polygon has no getonlySDF(pos_rel, Matrix3d) in the reference (Shape.hpp:1477), so no yaw kernels");
     if (kernel_size <= 0 || kernel_size % 2 == 0)

@@ -79,11 +79,9 @@ k_shape_kernels(ShapeParams sp, int ks, int count, double resu, int size_side, d
   const double y = resu * b - size_side * resu;
   double sn, cs;
   sincos_exact(yaw_tab[ind], &sn, &cs);
-  if constexpr (SHAPE == kPolygon) {
-    map[gid] = 0;
-  } else {
-    map[gid] = (shape_sdf_rot<SHAPE>(sp, x, y, cs, sn) <= safemargin) ? 1 : 0;
-  }
+  // (Polygon: consecutive lanes are consecutive cells b of one row a, so the wave's walk of svsdf_polygon.hpp sees
+  // neighbouring list cells)
+  map[gid] = (shape_sdf_rot<SHAPE>(sp, x, y, cs, sn) <= safemargin) ? 1 : 0;
 }
 
 // ---- yaw-kernel free-space table and batched A* successor test -------------------------------------------------------

@@ -252,9 +252,14 @@ __host__ __device__ __forceinline__ void poly_for_each(const PolyRec &rec, unsig
 // its record.  The lane's own path, taken by the lanes the first one cannot serve -- a query outside both grids (all
 // edges), a list longer than kPolyInline, a projection outside poly_quot's range, a crossing angle within 1e-9 rad of 0
 // or pi: the lists (or all edges) walked by the lane with the division and the reference's atan2 formula.
+//
+// Always inlined: every kernel was measured, and its register budget pinned (tests/test_kernel_resources.py), with this
+// body inside it.  Left to its heuristics the inliner did the same until the front end's three Polygon kernels joined the
+// translation unit; with their call sites it emitted poly_sdf<false> out of line for ALL callers (k_solve / k_round /
+// k_tail<Polygon> gained a call, 8 - 44 B of scratch each and the callee's 120 VGPRs).
 template <bool CLOSEST>
-__host__ __device__ inline double poly_sdf(const PolyAccel &pa, const PolyEdge *edges, double x, double y, double *cminx,
-                                           double *cminy) {
+__host__ __device__ __forceinline__ double poly_sdf(const PolyAccel &pa, const PolyEdge *edges, double x, double y, double *cminx,
+                                                    double *cminy) {
   unsigned base;
   const int cell = poly_locate(pa, x, y, base);
   // one 32-byte record per query: the cell's distance candidates and what it knows about the crossing parity

@@ -142,7 +142,7 @@ bool subsw_s(dim3 grid, hipStream_t st, ShapeParams sp, const double *father, co
 template <int S>
 bool shape_kernels_s(unsigned grid, hipStream_t st, ShapeParams sp, int ks, int count, double resu, int size_side,
                      double safemargin, const double *yaw, unsigned char *map) {
-  if constexpr (!shape_enabled<S>() || is_polygon<S>()) {   // Polygon has no (pos_rel, R_obj) overload (SHP:1477)
+  if constexpr (!shape_enabled<S>()) {   // (the Polygon: the host asks only under SVSDF_FLAG_POLYGON_YAW_KERNELS)
     return false;
   } else {
     hipLaunchKernelGGL((k_shape_kernels<S>), dim3(grid), dim3(kBlock), 0, st, sp, ks, count, resu, size_side, safemargin, yaw, map);
@@ -153,7 +153,7 @@ bool shape_kernels_s(unsigned grid, hipStream_t st, ShapeParams sp, int ks, int 
 template <int S>
 bool succ_s(unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const int *parent_ij, const double *parent_yaw,
             double *yaw_out, unsigned char *stage_out) {
-  if constexpr (!shape_enabled<S>() || is_polygon<S>()) {   // no yaw kernels for the Polygon (shape_kernels_s)
+  if constexpr (!shape_enabled<S>()) {
     return false;
   } else {
     hipLaunchKernelGGL((k_succ<S>), dim3(grid), dim3(kSuccBlock), 0, st, sp, fm, parent_ij, parent_yaw, yaw_out, stage_out);
@@ -163,7 +163,7 @@ bool succ_s(unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm
 
 template <int S>
 bool astar_s(hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const AstarDev &a, int slice) {
-  if constexpr (!shape_enabled<S>() || is_polygon<S>()) {   // no yaw kernels for the Polygon (shape_kernels_s)
+  if constexpr (!shape_enabled<S>()) {
     return false;
   } else {
     hipLaunchKernelGGL((k_astar<S>), dim3(1), dim3(kAstarBlock), 0, st, sp, fm, a, slice);   // one workgroup per search

@@ -387,17 +387,26 @@ __device__ __forceinline__ double shape_sdf(const ShapeParams &sp, double x, dou
 }
 
 // getonlySDF(pos_rel, R_obj) (2-argument overloads, e.g. SHP:545-559): ((pos_rel - trans) * Rotate *
-// R_obj).head(2) with R_obj = AngleAxisd(yaw, Z), i.e. the row vector times [[c,-s],[s,c]].  Not defined
-// for Polygon in the reference (SHP:1477 does not override the Matrix3d virtual).
+// R_obj).head(2) with R_obj = AngleAxisd(yaw, Z), i.e. the row vector times [[c,-s],[s,c]].
+// Polygon: the reference's two-argument overload takes a Matrix2d (SHP:1477-1500), so it does not override the Matrix3d
+// virtual and initShape's call lands in the empty base body (SHP:267): undefined there.  What is evaluated here is that
+// overload's own body (SHP:1484) -- the cell rotated by R_obj^T, no poly_params transform, then the edge loop and crossing
+// parity of the one-argument form -- with R_obj's upper-left block; only SVSDF_FLAG_POLYGON_YAW_KERNELS contexts reach it.
 template <int SHAPE>
 __device__ __forceinline__ double shape_sdf_rot(const ShapeParams &sp, double x, double y, double c, double s) {
-  static_assert(!is_polygon<SHAPE>(), "Polygon has no (pos_rel, R_obj) overload");
-  const double dx = x - sp.tx, dy = y - sp.ty;
-  const double qx = dx * sp.r00 + dy * sp.r10;
-  const double qy = dx * sp.r01 + dy * sp.r11;
-  const double px = qx * c + qy * s;
-  const double py = qx * (-s) + qy * c;
-  return shape_core<SHAPE>(sp, px, py);
+  static_assert(SHAPE != kPolygonLds, "the front end reads the Polygon's edges from global memory");
+  if constexpr (SHAPE == kPolygon) {
+    const double px = x * c + y * s;
+    const double py = x * (-s) + y * c;
+    return poly_sdf<false>(*sp.accel, sp.edges, px, py, nullptr, nullptr);
+  } else {
+    const double dx = x - sp.tx, dy = y - sp.ty;
+    const double qx = dx * sp.r00 + dy * sp.r10;
+    const double qy = dx * sp.r01 + dy * sp.r11;
+    const double px = qx * c + qy * s;
+    const double py = qx * (-s) + qy * c;
+    return shape_core<SHAPE>(sp, px, py);
+  }
 }
 
 // getonlyGrad1: central FD, dx = 1e-6 (SHP:35-53); Polygon: analytic (SHP:1505-1531).

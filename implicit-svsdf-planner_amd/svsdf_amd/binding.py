@@ -448,6 +448,7 @@ FLAG_KEEP_INPUT_ORDER = 1
 FLAG_HOST_ONLY = 2
 FLAG_EXACT_PIECE_TIME = 4
 FLAG_FAST_PIECE_TIME = 8
+FLAG_POLYGON_YAW_KERNELS = 16   # Polygon contexts: yaw kernels and the front end (svsdf_c.h)
 COMBINE_AUTO, COMBINE_HOST, COMBINE_RCCL = 0, 1, 2
 
 

@@ -15,7 +15,8 @@ import os
 
 import numpy as np
 
-from .binding import SvsdfContext, SvsdfError, shape_id_from_inputdata, SHAPES, mesh_section_obj
+from .binding import (SvsdfContext, SvsdfError, shape_id_from_inputdata, SHAPES, mesh_section_obj,
+                      FLAG_POLYGON_YAW_KERNELS)
 
 
 def _dist():
@@ -29,7 +30,11 @@ def _dist():
 
 
 class TrajOptimizer:
-    def __init__(self):
+    def __init__(self, polygon_front_end=False):
+        """polygon_front_end: a Polygon context built from a mesh `inputdata` (or a given `polygon`) is created with
+        FLAG_POLYGON_YAW_KERNELS, so that frontend_set_map / astar_search work on it (svsdf_c.h: the reference's stated
+        intent for the Polygon's yaw kernels, not its undefined behaviour).  No effect on the analytic shapes."""
+        self.polygon_front_end = bool(polygon_front_end)
         # Config-derived members (BEO:69-95)
         self.rho = 3.8
         self.weight_p = 60.0
@@ -124,10 +129,11 @@ class TrajOptimizer:
                     polygon, polygon_loops = mesh_section_obj(path)
             dist = _dist()
             rank, ws = (dist.get_rank(), dist.get_world_size()) if dist else (0, 1)
+            flags = FLAG_POLYGON_YAW_KERNELS if self.polygon_front_end and sid == SHAPES.index("Polygon") else 0
             self._ctx = SvsdfContext(shape=sid, safety_hor=self.safety_hor, weight_p=self.weight_p,
                                      rho=self.rho, poly_params=self.poly_params, polygon=polygon,
                                      head_state=self.initState, tail_state=self.finalState,
-                                     device=self.device, rank=rank, world_size=ws,
+                                     device=self.device, rank=rank, world_size=ws, flags=flags,
                                      devices=self.devices, combine=self.combine, polygon_loops=polygon_loops)
             if self._scale is not None:
                 self._ctx.set_scale(**self._scale)

@@ -127,6 +127,20 @@ typedef struct svsdf_config {
                                          durations, which flat stretches of SDF(t) amplify (differential fuzzing: gradient
                                          up to 5e-5 relative off, vs 1e-5 with the chain); round 1's behaviour */
 
+/* Yaw kernels, and with them the whole front end, for a Polygon context (a given outline or the SWM:363-369 fallback
+ * rectangle).  Without this flag svsdf_shape_kernels and svsdf_frontend_set_map refuse a Polygon: BasicShape::initShape
+ * (Shape.hpp:386-430) calls getonlySDF(pos, Matrix3d), Polygon's two-argument overload takes a Matrix2d
+ * (Shape.hpp:1477-1500), so the virtual call lands in the empty base body (Shape.hpp:267) and the reference's result is
+ * undefined.  With it, cell (x, y) of yaw kernel k is occupied iff
+ *   Polygon::getonlySDF((x c + y s, x (-s) + y c)) <= safemargin,   (s, c) = sincos(yaw_k):
+ * the body of that overload (Shape.hpp:1484: the cell rotated by R_obj^T, then the same edge loop and the same crossing
+ * parity as the one-argument form, Shape.hpp:1448-1476) with R_obj = the upper-left block of AngleAxisd(yaw_k, Z).  No
+ * poly_params transform is applied, as in the one-argument form.  This is the reference's stated intent, not its
+ * (undefined) behaviour.  Everything else is as for the analytic shapes: yaw table, generateByteKernel packing, the
+ * limits of svsdf_frontend_set_map, stages 0 - 4, the A* ordering, slicing, counters.  On a context of any other shape
+ * the flag is accepted and has no effect. */
+#define SVSDF_FLAG_POLYGON_YAW_KERNELS 16
+
 typedef struct svsdf_ctx svsdf_ctx;
 
 /* ---- lifetime ---------------------------------------------------------------------------- */
@@ -267,7 +281,8 @@ int svsdf_check_sub_sw_collision(svsdf_ctx *ctx, size_t n_edges, const double *f
  * ((kernel_size+7)/8) bytes, bit (0x80 >> b%8) of byte [k][a][b/8]; yaw_out (may be NULL): kernel_count yaws;
  * loop_count (may be NULL): iterations the reference loop makes (kernel_count, or kernel_count+1 when
  * rounding lets the last yaw stay below PI -- the reference then writes past its arrays; only kernel_count
- * kernels are produced here).  Polygon -> SVSDF_ERR_INVALID (no such overload in the reference). */
+ * kernels are produced here).  Polygon -> SVSDF_ERR_INVALID (no such overload in the reference), unless the context
+ * was created with SVSDF_FLAG_POLYGON_YAW_KERNELS (the definition is given there). */
 int svsdf_shape_kernels(svsdf_ctx *ctx, int kernel_size, int kernel_count, double kernel_resolution,
                         double safemargin, unsigned char *map_out, unsigned char *bytes_out, double *yaw_out,
                         int *loop_count);
@@ -307,7 +322,7 @@ int svsdf_pcd_read_ascii(const char *path, float *xyz, size_t capacity, size_t *
  * (Y + 2 side) with side = (kernel_size - 1) / 2, the cell index itself is the box's minimum corner in it, outside the
  * map is free, and the bits the reference reads past a row only meet kernel columns >= kernel_size, which are zero.
  * The bitmap, the grid geometry and the table stay resident in the context until the next call or svsdf_destroy.
- * SVSDF_ERR_INVALID with a message: Polygon (as in svsdf_shape_kernels), an even or non-positive kernel_size,
+ * SVSDF_ERR_INVALID with a message: Polygon without SVSDF_FLAG_POLYGON_YAW_KERNELS (as in svsdf_shape_kernels), an even or non-positive kernel_size,
  * kernel_size > 63 or kernel_count > 64 (a kernel row and a cell's mask are one word each; the reference's yaml has
  * 17 and 18), a null or empty map.  A multi-device context uses its first device, like the other front-end entries. */
 int svsdf_frontend_set_map(svsdf_ctx *ctx, const svsdf_map *map, int kernel_size, int kernel_count, double safemargin);

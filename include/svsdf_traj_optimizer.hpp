@@ -52,6 +52,8 @@ class TrajOptimizerHip {
   int rank = 0, world_size = 1;
   std::vector<int> devices;        // >= 2 entries: in-process multi-GPU (svsdf_config::n_devices / devices); 1 entry: that device
   int combine = SVSDF_COMBINE_AUTO;
+  bool polygon_front_end = false;  // a Polygon context (mesh inputdata, polygon_xy) is created with
+                                   // SVSDF_FLAG_POLYGON_YAW_KERNELS: svsdf_frontend_set_map / svsdf_astar_search work on it
 
   // --- optimisation state (BEO:44-60) ---
   int pieceN = 0, temporalDim = 0, spatialDim = 0;
@@ -231,6 +233,7 @@ class TrajOptimizerHip {
       std::memcpy(cfg.tail_state, finalState, sizeof(finalState));
       cfg.device = device; cfg.rank = rank; cfg.world_size = world_size;
       cfg.combine = combine;
+      if (polygon_front_end && cfg.shape_id == SVSDF_SHAPE_Polygon) cfg.flags |= SVSDF_FLAG_POLYGON_YAW_KERNELS;
       if (devices.size() == 1 && combine != SVSDF_COMBINE_RCCL) cfg.device = devices[0];
       else if (!devices.empty() && devices.size() <= SVSDF_MAX_DEVICES) {
         cfg.n_devices = (int)devices.size();
@@ -260,6 +263,7 @@ class TrajOptimizerHip {
     add(&rho, sizeof rho); add(&weight_p, sizeof weight_p); add(&safety_hor, sizeof safety_hor);
     add(poly_params, sizeof poly_params); add(&device, sizeof device); add(&rank, sizeof rank);
     add(&world_size, sizeof world_size); add(&combine, sizeof combine);
+    add(&polygon_front_end, sizeof polygon_front_end);
     if (!devices.empty()) add(devices.data(), devices.size() * sizeof(int));
     k += "|";
     if (!polygon_xy.empty()) add(polygon_xy.data(), polygon_xy.size() * sizeof(double));
