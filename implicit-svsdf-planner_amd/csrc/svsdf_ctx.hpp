@@ -173,6 +173,18 @@ struct FrontMap {
   svsdf::AstarDev astar{};
   bool searched = false;                      // the node records hold a search on this map
 };
+// The device-resident occupancy map (svsdf_map_build_device; svsdf_mapdev.hpp) and the last gather from it.  It lives on a
+// multi-device context's first device.  Releasing it is assigning a fresh one.
+struct ResidentMap {
+  bool set = false;
+  int dims[3] = {0, 0, 0};
+  double bmin[3] = {0, 0, 0}, bmax[3] = {0, 0, 0}, res = 1.0;
+  int sta_threshold = 0;
+  size_t n_cloud = 0, cells = 0, occupied = 0, gathered = 0;
+  double build_ms = 0.0, gather_ms = 0.0;
+  Buf<unsigned char> d_occ;                   // cells bytes, [(i * Y + j) * Z + k]
+  Buf<double> d_pts;                          // the last gather: 3 * gathered doubles, ascending unified voxel id
+};
 // Staging that outlives a map change, grown on demand
 struct FrontStaging {
   Staged<double> edges;                       // svsdf_check_sub_sw_collision: svsdf_layout::subsw_layout
@@ -312,6 +324,7 @@ struct svsdf_ctx {
   // front end (row f3; svsdf_extras.hip alone): the resident map, and the staging that outlives it
   svsdf_impl::FrontMap fmap;
   svsdf_impl::FrontStaging fstage;
+  svsdf_impl::ResidentMap rmap;     // svsdf_map_build_device (svsdf_extras.hip alone)
 
   // profiling
   bool profile = false;  // per-launch HIP events (env SVSDF_PROFILE=1 or svsdf_set_profiling)

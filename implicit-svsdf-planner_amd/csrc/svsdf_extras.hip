@@ -1,5 +1,6 @@
 // svsdf_extras.hip -- C ABI of the rows around the hot path: batched front-end collision check and
-// shape byte kernels (SWM:1171-1211, SHP:386-430), query-point producer (PCSmap_manager.cpp:88-210), mesh outline, the
+// shape byte kernels (SWM:1171-1211, SHP:386-430), query-point producer (PCSmap_manager.cpp:88-210) on the host and on the
+// device (svsdf_mapdev.hpp), mesh outline, the
 // swept volume's outline and its extrusion (SWM:321-336), the in-repo L-BFGS driver (lbfgs.hpp:290-438).
 // The device entries open with on_device (svsdf_ctx.hpp); their packed buffers are laid out in svsdf_layout.hpp.
 #include "svsdf_ctx.hpp"
@@ -7,6 +8,7 @@
 #include "svsdf_mesh.hpp"
 #include "svsdf_contour.hpp"
 #include "svsdf_points.hpp"
+#include "svsdf_mapdev.hpp"
 
 using namespace svsdf;
 using namespace svsdf_impl;
@@ -68,6 +70,85 @@ template <typename... T> static bool deliver(const Out<T> &...o) {
   if (!(... && (o.capacity >= *o.count))) return false;
   (std::copy(o.v.begin(), o.v.end(), o.out), ...);
   return true;
+}
+
+// The grid a front-end map is made from: the host map's (svsdf_frontend_set_map) or the resident one's (svsdf_frontend_set_map_device)
+struct FrontGrid { int X, Y, Z; double res; const double *bmin, *bmax; };
+
+// What the two set-map entries share: the argument checks (`what` names the entry in every message), then the yaw kernels,
+// their row words, the yaw-free table and the FrontMapDev fill.  `fill_occ(d_occ, side, row_words, rows)` queues the inflated
+// layer-0 bitmap into d_occ on the context's stream, between the yaw table's upload and the kernels' launch.
+static int frontend_install(svsdf_ctx *ctx, const std::string &what, const FrontGrid &g, int kernel_size, int kernel_count,
+                            double safemargin, const std::function<int(unsigned long long *, int, int, size_t)> &fill_occ) {
+  if (polygon_refused(ctx))
+    return fail(ctx, SVSDF_ERR_INVALID,
+                what + ": Polygon has no getonlySDF(pos_rel, Matrix3d) in the reference (Shape.hpp:1477), so no yaw kernels");
+  if (kernel_size <= 0 || kernel_size % 2 == 0)
+    return fail(ctx, SVSDF_ERR_INVALID, what + ": kernel_size must be odd and positive");
+  if (kernel_size > kMaxKernelSize || kernel_count > kMaxKernelCount || kernel_count < 1)
+    return fail(ctx, SVSDF_ERR_INVALID,
+                what + ": kernel_size <= 63 and 1 <= kernel_count <= 64 (a kernel row and a cell's mask are one word each)");
+  if (!std::isfinite(safemargin)) return fail(ctx, SVSDF_ERR_INVALID, what + ": safemargin not finite");
+  const int X = g.X, Y = g.Y, Z = g.Z;
+  const int side = (kernel_size - 1) / 2;
+  if (X < 1 || Y < 1 || Z < 1) return fail(ctx, SVSDF_ERR_INVALID, what + ": empty map");
+  if ((Y + kYawFreeBlock - 1) / kYawFreeBlock > 65535 || (long long)X * Y > 0x7fffffffll)
+    return fail(ctx, SVSDF_ERR_INVALID, what + ": map too large");
+  int loops = 0;
+  const std::vector<double> yaws = shape_kernel_yaws(kernel_count, &loops);
+  if ((int)yaws.size() != kernel_count)
+    return fail(ctx, SVSDF_ERR_INVALID, what + ": the reference's yaw loop yields fewer kernels than kernel_count");
+  const int row_words = (Y + 2 * side + 63) / 64 + 1;
+  const size_t rows = (size_t)X + 2 * (size_t)side;
+  double kt_tab[kMaxKt];
+  const int nkt = subsw_kt_table(kt_tab);
+
+  HIPCHK(hipSetDevice(ctx->device));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  FrontMap &fm = ctx->fmap;
+  fm = FrontMap{};   // the old map goes, and its search state with it
+  Buf<double> d_yaw;
+  Buf<unsigned char> d_bytes;
+  Buf<unsigned long long> d_krows;
+  hipStream_t st = ctx->stream;
+  const std::string uncompiled = what + ": shape not compiled into this library";
+  const auto build = [&]() -> int {
+    int rc = d_yaw.alloc(ctx, kernel_count);
+    if (rc == SVSDF_OK) rc = d_bytes.alloc(ctx, (size_t)kernel_size * kernel_size * kernel_count);
+    if (rc == SVSDF_OK) rc = d_krows.alloc(ctx, (size_t)kernel_size * kernel_count);
+    if (rc == SVSDF_OK) rc = fm.d_occ.alloc(ctx, rows * row_words);
+    if (rc == SVSDF_OK) rc = fm.d_free.alloc(ctx, (size_t)X * Y);
+    if (rc == SVSDF_OK) rc = fm.d_kt.alloc(ctx, kMaxKt);
+    if (rc) return rc;
+    // the kernel resolution is the map's: kernelConv overlays kernel cells on map cells one to one
+    rc = build_yaw_kernels(ctx, what.c_str(), uncompiled.c_str(), yaws, kernel_size, g.res, side, safemargin, d_yaw, d_bytes, [&]() -> int {
+      const int rf = fill_occ(fm.d_occ, side, row_words, rows);
+      if (rf) return rf;
+      HIPCHK_AS(what, hipMemcpyAsync(fm.d_kt, kt_tab, kMaxKt * sizeof(double), hipMemcpyHostToDevice, st));
+      return SVSDF_OK;
+    });
+    if (rc) return rc;
+    launch_k_pack_kernel_rows(st, d_bytes, kernel_size, kernel_count, d_krows);
+    HIPCHK_AS(what, hipGetLastError());
+    launch_k_yaw_free(st, fm.d_occ, row_words, d_krows, kernel_size, kernel_count, X, Y, fm.d_free);
+    HIPCHK_AS(what, hipGetLastError());
+    return SVSDF_OK;
+  };
+  int rc = build();
+  // on every path: the pageable sources above and the scratch must outlive what the stream still does with them
+  const hipError_t es = hipStreamSynchronize(st);
+  if (rc == SVSDF_OK && es != hipSuccess)
+    rc = fail(ctx, SVSDF_ERR_HIP_BASE + (int)es, what + ": " + hipGetErrorString(es));
+  if (rc) { fm = FrontMap{}; return rc; }
+  FrontMapDev &dev = fm.dev;
+  dev.occ = fm.d_occ; dev.free_ = fm.d_free; dev.kt = fm.d_kt; dev.nkt = nkt;
+  dev.X = X; dev.Y = Y; dev.side = side; dev.row_words = row_words; dev.kernel_count = kernel_count;
+  dev.res = g.res;
+  dev.half = (double)(kernel_size / 2 + 1);   // front_end_Astar.hpp:224: integer division, metres
+  for (int d = 0; d < 3; ++d) { dev.bmin[d] = g.bmin[d]; dev.bmax[d] = g.bmax[d]; }
+  fm.Z = Z;
+  fm.set = true;
+  return SVSDF_OK;
 }
 
 extern "C" {
@@ -213,81 +294,150 @@ int svsdf_pcd_read_ascii(const char *path, float *xyz, size_t capacity, size_t *
 int svsdf_frontend_set_map(svsdf_ctx *group, const svsdf_map *map, int kernel_size, int kernel_count, double safemargin) {
   return on_device(group, __func__, [&](svsdf_ctx *ctx) -> int {
     if (!map) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: null map");
-    if (polygon_refused(ctx))
-      return fail(ctx, SVSDF_ERR_INVALID,
-                  "svsdf_frontend_set_map: Polygon has no getonlySDF(pos_rel, Matrix3d) in the reference (Shape.hpp:1477), so no yaw kernels");
-    if (kernel_size <= 0 || kernel_size % 2 == 0)
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: kernel_size must be odd and positive");
-    if (kernel_size > kMaxKernelSize || kernel_count > kMaxKernelCount || kernel_count < 1)
-      return fail(ctx, SVSDF_ERR_INVALID,
-                  "svsdf_frontend_set_map: kernel_size <= 63 and 1 <= kernel_count <= 64 (a kernel row and a cell's mask are one word each)");
-    if (!std::isfinite(safemargin)) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: safemargin not finite");
     const svsdf_host::OccupancyMap &m = map->m;
-    const int X = m.dims()[0], Y = m.dims()[1], Z = m.dims()[2];
-    const int side = (kernel_size - 1) / 2;
-    if (X < 1 || Y < 1 || Z < 1) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: empty map");
-    if ((Y + kYawFreeBlock - 1) / kYawFreeBlock > 65535 || (long long)X * Y > 0x7fffffffll)
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: map too large");
-    int loops = 0;
-    const std::vector<double> yaws = shape_kernel_yaws(kernel_count, &loops);
-    if ((int)yaws.size() != kernel_count)
-      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map: the reference's yaw loop yields fewer kernels than kernel_count");
+    const FrontGrid g{m.dims()[0], m.dims()[1], m.dims()[2], m.resolution(), m.bmin(), m.bmax()};
     // generateMapKernel2D (PCSmap_manager.h:81-108) in 64-bit row words: layer iz = 0, cell (x, y) at (x + side, y + side)
-    const int row_words = (Y + 2 * side + 63) / 64 + 1;
-    const size_t rows = (size_t)X + 2 * (size_t)side;
-    std::vector<unsigned long long> occ(rows * row_words, 0ull);
-    for (int x = 0; x < X; ++x)
-      for (int y = 0; y < Y; ++y)
-        if (m.cell(x, y, 0)) occ[(size_t)(x + side) * row_words + ((y + side) >> 6)] |= 1ull << ((y + side) & 63);
-    double kt_tab[kMaxKt];
-    const int nkt = subsw_kt_table(kt_tab);
+    std::vector<unsigned long long> occ;   // pageable: frontend_install synchronises the stream on every path after the upload
+    return frontend_install(ctx, "svsdf_frontend_set_map", g, kernel_size, kernel_count, safemargin,
+                            [&](unsigned long long *d_occ, int side, int row_words, size_t rows) -> int {
+      occ.assign(rows * row_words, 0ull);
+      for (int x = 0; x < g.X; ++x)
+        for (int y = 0; y < g.Y; ++y)
+          if (m.cell(x, y, 0)) occ[(size_t)(x + side) * row_words + ((y + side) >> 6)] |= 1ull << ((y + side) & 63);
+      HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(d_occ, occ.data(), occ.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
+      return SVSDF_OK;
+    });
+  });
+}
 
+// ---- the producer on the device (svsdf_mapdev.hpp): cloud -> resident map -> front-end bitmap / gathered query points ------
+int svsdf_map_build_device(svsdf_ctx *group, const float *xyz, size_t n, int xyz_on_device, double resolution, int sta_threshold) {
+  return on_device(group, __func__, [&](svsdf_ctx *ctx) -> int {
+    if (!xyz && n) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_build_device: null cloud");
+    if (!(resolution > 0.0) || !std::isfinite(resolution))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_build_device: resolution must be positive and finite");
+    if (n > 0xffffffffull) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_build_device: too many points (n >= 2^32)");
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    FrontMap &fm = ctx->fmap;
-    fm = FrontMap{};   // the old map goes, and its search state with it
-    Buf<double> d_yaw;
-    Buf<unsigned char> d_bytes;
-    Buf<unsigned long long> d_krows;
-    hipStream_t st = ctx->stream;
-    const auto build = [&]() -> int {
-      int rc = d_yaw.alloc(ctx, kernel_count);
-      if (rc == SVSDF_OK) rc = d_bytes.alloc(ctx, (size_t)kernel_size * kernel_size * kernel_count);
-      if (rc == SVSDF_OK) rc = d_krows.alloc(ctx, (size_t)kernel_size * kernel_count);
-      if (rc == SVSDF_OK) rc = fm.d_occ.alloc(ctx, occ.size());
-      if (rc == SVSDF_OK) rc = fm.d_free.alloc(ctx, (size_t)X * Y);
-      if (rc == SVSDF_OK) rc = fm.d_kt.alloc(ctx, kMaxKt);
+    const auto t0 = std::chrono::steady_clock::now();
+    ctx->rmap = ResidentMap{};   // the earlier map goes whatever becomes of this call
+    Buf<float> d_stage;
+    const float *d_cloud = xyz;
+    if (n && !xyz_on_device) {
+      int rc = d_stage.alloc(ctx, 3 * n);
       if (rc) return rc;
-      // the kernel resolution is the map's: kernelConv overlays kernel cells on map cells one to one
-      rc = build_yaw_kernels(ctx, "svsdf_frontend_set_map", "svsdf_frontend_set_map: shape not compiled into this library", yaws,
-                             kernel_size, m.resolution(), side, safemargin, d_yaw, d_bytes, [&]() -> int {
-        HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(fm.d_occ, occ.data(), occ.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-        HIPCHK_AS("svsdf_frontend_set_map", hipMemcpyAsync(fm.d_kt, kt_tab, kMaxKt * sizeof(double), hipMemcpyHostToDevice, st));
-        return SVSDF_OK;
-      });
-      if (rc) return rc;
-      launch_k_pack_kernel_rows(st, d_bytes, kernel_size, kernel_count, d_krows);
-      HIPCHK_AS("svsdf_frontend_set_map", hipGetLastError());
-      launch_k_yaw_free(st, fm.d_occ, row_words, d_krows, kernel_size, kernel_count, X, Y, fm.d_free);
-      HIPCHK_AS("svsdf_frontend_set_map", hipGetLastError());
-      return SVSDF_OK;
-    };
-    int rc = build();
-    // on every path: the pageable sources above and the scratch must outlive what the stream still does with them
-    const hipError_t es = hipStreamSynchronize(st);
+      HIPCHK_AS("svsdf_map_build_device", hipMemcpyAsync(d_stage, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+      d_cloud = d_stage;
+    }
+    int rc = map_build(ctx, d_cloud, n, resolution, sta_threshold);
+    // on every path: the caller's (pageable) cloud and the staging must outlive what the stream still does with them
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
     if (rc == SVSDF_OK && es != hipSuccess)
-      rc = fail(ctx, SVSDF_ERR_HIP_BASE + (int)es, std::string("svsdf_frontend_set_map: ") + hipGetErrorString(es));
-    if (rc) { fm = FrontMap{}; return rc; }
-    FrontMapDev &dev = fm.dev;
-    dev.occ = fm.d_occ; dev.free_ = fm.d_free; dev.kt = fm.d_kt; dev.nkt = nkt;
-    dev.X = X; dev.Y = Y; dev.side = side; dev.row_words = row_words; dev.kernel_count = kernel_count;
-    dev.res = m.resolution();
-    dev.half = (double)(kernel_size / 2 + 1);   // front_end_Astar.hpp:224: integer division, metres
-    for (int d = 0; d < 3; ++d) { dev.bmin[d] = m.bmin()[d]; dev.bmax[d] = m.bmax()[d]; }
-    fm.Z = Z;
-    fm.set = true;
+      rc = fail(ctx, SVSDF_ERR_HIP_BASE + (int)es, std::string("svsdf_map_build_device: ") + hipGetErrorString(es));
+    if (rc) { ctx->rmap = ResidentMap{}; return rc; }
+    ctx->rmap.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SVSDF_OK;
   });
+}
+
+int svsdf_map_device_get_info(const svsdf_ctx *group, svsdf_map_device_info *out) {
+  return on_device(const_cast<svsdf_ctx *>(group), __func__, [&](svsdf_ctx *ctx) -> int {
+    if (!out) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_device_get_info: null argument");
+    if (out->struct_size != (int)sizeof(svsdf_map_device_info))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_device_get_info: out->struct_size is not sizeof(svsdf_map_device_info)");
+    const ResidentMap &rm = ctx->rmap;
+    if (!rm.set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_device_get_info: no resident map (svsdf_map_build_device)");
+    for (int d = 0; d < 3; ++d) { out->dims[d] = rm.dims[d]; out->bmin[d] = rm.bmin[d]; out->bmax[d] = rm.bmax[d]; }
+    out->resolution = rm.res; out->sta_threshold = rm.sta_threshold;
+    out->n_cloud = rm.n_cloud; out->occupied = rm.occupied; out->gathered = rm.gathered;
+    out->build_ms = rm.build_ms; out->gather_ms = rm.gather_ms;
+    return SVSDF_OK;
+  });
+}
+
+int svsdf_map_device_cells(const svsdf_ctx *group, unsigned char *occ_out, size_t capacity) {
+  return on_device(const_cast<svsdf_ctx *>(group), __func__, [&](svsdf_ctx *ctx) -> int {
+    const ResidentMap &rm = ctx->rmap;
+    if (!rm.set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_device_cells: no resident map (svsdf_map_build_device)");
+    if (rm.cells == 0) return SVSDF_OK;
+    if (!occ_out || capacity < rm.cells)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_device_cells: capacity too small (X * Y * Z bytes, svsdf_map_device_get_info)");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(occ_out, rm.d_occ, rm.cells, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SVSDF_OK;
+  });
+}
+
+int svsdf_frontend_set_map_device(svsdf_ctx *group, int kernel_size, int kernel_count, double safemargin) {
+  return on_device(group, __func__, [&](svsdf_ctx *ctx) -> int {
+    const ResidentMap &rm = ctx->rmap;
+    if (!rm.set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_frontend_set_map_device: no resident map (svsdf_map_build_device)");
+    const FrontGrid g{rm.dims[0], rm.dims[1], rm.dims[2], rm.res, rm.bmin, rm.bmax};
+    return frontend_install(ctx, "svsdf_frontend_set_map_device", g, kernel_size, kernel_count, safemargin,
+                            [&](unsigned long long *d_occ, int side, int row_words, size_t rows) -> int {
+      return map_front_bitmap(ctx, "svsdf_frontend_set_map_device", side, row_words, rows, d_occ);
+    });
+  });
+}
+
+int svsdf_set_points_from_map(svsdf_ctx *ctx, const double *centres_xyz, size_t ncentres, const double halfbd[3], size_t *count) {
+  if (!ctx || ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "svsdf_set_points_from_map: no device context");
+  if ((!centres_xyz && ncentres) || !halfbd) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_set_points_from_map: null argument");
+  for (size_t e = 0; e < 3 * ncentres; ++e)
+    if (!std::isfinite(centres_xyz[e])) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_set_points_from_map: non-finite centre");
+  for (int d = 0; d < 3; ++d)
+    if (!std::isfinite(halfbd[d])) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_set_points_from_map: non-finite half extent");
+  svsdf_ctx *leaf = leaf_of(ctx);   // the map lives on the first device
+  ResidentMap &rm = leaf->rmap;
+  if (!rm.set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_set_points_from_map: no resident map (svsdf_map_build_device)");
+  const auto t0 = std::chrono::steady_clock::now();
+  int rc = SVSDF_OK;
+  if (hipSetDevice(leaf->device) != hipSuccess || hipStreamSynchronize(leaf->stream) != hipSuccess)
+    rc = fail(leaf, SVSDF_ERR_HIP_BASE, "svsdf_set_points_from_map: the map's device is not usable");
+  if (rc == SVSDF_OK) rc = map_gather(leaf, centres_xyz, ncentres, halfbd);
+  if (rc) {
+    (void)hipStreamSynchronize(leaf->stream);
+    rm.gathered = 0;
+    rm.d_pts.reset();
+    if (leaf != ctx) ctx->err = leaf->err;
+    return rc;
+  }
+  rm.gather_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  // the hand-over: the compacted array is the planner's input as it stands (svsdf_set_points_device's path)
+  const size_t P = rm.gathered;
+  rc = ctx->subs.empty() ? upload_shard_device(ctx, rm.d_pts, P, ctx->cfg.rank, ctx->cfg.world_size)
+                         : upload_group_device(ctx, rm.d_pts, P);
+  ctx->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  for (svsdf_ctx *s : ctx->subs) s->setup_ms = ctx->setup_ms;
+  if (count) *count = P;
+  return rc;
+}
+
+int svsdf_map_device_points(const svsdf_ctx *group, double *out_xyz, size_t capacity, size_t *count) {
+  return on_device(const_cast<svsdf_ctx *>(group), __func__, [&](svsdf_ctx *ctx) -> int {
+    const ResidentMap &rm = ctx->rmap;
+    if (!rm.set) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_device_points: no resident map (svsdf_map_build_device)");
+    if (!count) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_device_points: null count");
+    *count = rm.gathered;
+    if (!out_xyz || rm.gathered == 0) return SVSDF_OK;   // the size query
+    if (capacity < rm.gathered)
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_map_device_points: capacity too small (query with out_xyz = NULL first)");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipMemcpyAsync(out_xyz, rm.d_pts, 3 * rm.gathered * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return SVSDF_OK;
+  });
+}
+
+// plan_manager.cpp:132-140 and the loop header of :157; pure host
+int svsdf_path_waypoints(size_t path_len, double grid_resolution, double traj_parlength, size_t *idx_out, size_t capacity,
+                         size_t *count, int *index_gap) {
+  std::vector<size_t> idx;
+  int gap = 0;
+  if (!count || !svsdf_host::path_waypoints(path_len, grid_resolution, traj_parlength, idx, &gap)) return SVSDF_ERR_INVALID;
+  if (index_gap) *index_gap = gap;
+  return deliver(Out<size_t>{idx, 1, idx_out, capacity, count}) ? SVSDF_OK : SVSDF_ERR_INVALID;
 }
 
 int svsdf_frontend_yaw_free(const svsdf_ctx *group, unsigned long long *mask_out, size_t capacity, int dims2[2]) {

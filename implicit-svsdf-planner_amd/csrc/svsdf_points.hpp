@@ -22,7 +22,73 @@
 
 namespace svsdf_host {
 
-class OccupancyMap {
+// The grid's geometry and the index arithmetic on it, without the cells: what the host map below and the device-resident map
+// (svsdf_mapdev.hpp) share.  The device map builds one from the bounds it reads back and takes its waypoint boxes from here.
+struct GridGeometry {
+  // GRD:29-31 from bounds already in bmin_ / bmax_
+  void set_resolution(double resolution) {
+    res_ = resolution;
+    for (int d = 0; d < 3; ++d) size_[d] = (int)std::ceil((bmax_[d] - bmin_[d]) / res_);  // GRD:29-31
+  }
+  size_t cells() const { return (size_t)std::max(0, size_[0]) * std::max(0, size_[1]) * std::max(0, size_[2]); }
+  // The index boxes of plan_manager.cpp:156-167 around PCH:184-219, 12 ints per centre: c1, c2 of the centre, l1, l2 of the
+  // previous one (the first "previous" is tmp_pos = (999, 999, 999))
+  void centre_boxes(const double *centres, size_t n, const double halfbd[3], std::vector<int> &boxes) const {
+    boxes.resize(12 * n);
+    double last[3] = {999.0, 999.0, 999.0};  // tmp_pos
+    for (size_t c = 0; c < n; ++c) {
+      const double *ctr = centres + 3 * c;
+      int *b = boxes.data() + 12 * c;
+      box_ids(ctr, halfbd, b, b + 3);
+      box_ids(last, halfbd, b + 6, b + 9);
+      std::memcpy(last, ctr, sizeof(last));
+    }
+  }
+
+  bool in_map(double x, double y, double z) const {  // GRD:43-71
+    return !(x < bmin_[0] || y < bmin_[1] || z < bmin_[2] || x > bmax_[0] || y > bmax_[1] || z > bmax_[2]);
+  }
+  // GRD:137-177, including its clamping quirk (a negative iy / iz resets ix)
+  void grid_index(double x, double y, double z, int id[3]) const {
+    if (!in_map(x, y, z)) { id[0] = id[1] = id[2] = 0; return; }
+    int ix = (int)std::floor((x - bmin_[0]) / res_);
+    int iy = (int)std::floor((y - bmin_[1]) / res_);
+    int iz = (int)std::floor((z - bmin_[2]) / res_);
+    if (ix < 0) ix = 0;
+    if (ix >= size_[0]) ix = size_[0] - 1;
+    if (iy < 0) ix = 0;
+    if (iy >= size_[1]) iy = size_[1] - 1;
+    if (iz < 0) ix = 0;
+    if (iz >= size_[2]) iz = size_[2] - 1;
+    id[0] = ix; id[1] = iy; id[2] = iz;
+  }
+  void box_ids(const double ctr[3], const double halfbd[3], int c1[3], int c2[3]) const {
+    double a[3], b[3];
+    for (int d = 0; d < 3; ++d) {  // projInMap PCH:128-135
+      a[d] = ctr[d] - halfbd[d];
+      b[d] = ctr[d] + halfbd[d];
+      if (a[d] < bmin_[d]) a[d] = bmin_[d];
+      if (a[d] > bmax_[d]) a[d] = bmax_[d];
+      if (b[d] < bmin_[d]) b[d] = bmin_[d];
+      if (b[d] > bmax_[d]) b[d] = bmax_[d];
+    }
+    grid_index(a[0], a[1], a[2], c1);
+    grid_index(b[0], b[1], b[2], c2);
+  }
+  size_t addr(int i, int j, int k) const { return ((size_t)i * size_[1] + j) * size_[2] + k; }  // GridMap3D.h:129-130
+  void cube_center(int i, int j, int k, double p[3]) const {  // GRD:184-195
+    if (i < 0 || i >= size_[0] || j < 0 || j >= size_[1] || k < 0 || k >= size_[2]) { p[0] = p[1] = p[2] = 0.0; return; }
+    p[0] = (i + 0.5) * res_ + bmin_[0];
+    p[1] = (j + 0.5) * res_ + bmin_[1];
+    p[2] = (k + 0.5) * res_ + bmin_[2];
+  }
+
+  double res_ = 1.0;
+  double bmin_[3] = {0, 0, 0}, bmax_[3] = {0, 0, 0};
+  int size_[3] = {0, 0, 0};
+};
+
+class OccupancyMap : private GridGeometry {
  public:
   // PCS:116-178: bounds from the cloud (floats widened to double), grid of `resolution`, a voxel is
   // occupied when it holds >= sta_threshold points.
@@ -90,54 +156,38 @@ class OccupancyMap {
   bool cell(int i, int j, int k) const { return occ_[addr(i, j, k)] != 0; }
 
  private:
-  bool in_map(double x, double y, double z) const {  // GRD:43-71
-    return !(x < bmin_[0] || y < bmin_[1] || z < bmin_[2] || x > bmax_[0] || y > bmax_[1] || z > bmax_[2]);
-  }
-  // GRD:137-177, including its clamping quirk (a negative iy / iz resets ix)
-  void grid_index(double x, double y, double z, int id[3]) const {
-    if (!in_map(x, y, z)) { id[0] = id[1] = id[2] = 0; return; }
-    int ix = (int)std::floor((x - bmin_[0]) / res_);
-    int iy = (int)std::floor((y - bmin_[1]) / res_);
-    int iz = (int)std::floor((z - bmin_[2]) / res_);
-    if (ix < 0) ix = 0;
-    if (ix >= size_[0]) ix = size_[0] - 1;
-    if (iy < 0) ix = 0;
-    if (iy >= size_[1]) iy = size_[1] - 1;
-    if (iz < 0) ix = 0;
-    if (iz >= size_[2]) iz = size_[2] - 1;
-    id[0] = ix; id[1] = iy; id[2] = iz;
-  }
-  void box_ids(const double ctr[3], const double halfbd[3], int c1[3], int c2[3]) const {
-    double a[3], b[3];
-    for (int d = 0; d < 3; ++d) {  // projInMap PCH:128-135
-      a[d] = ctr[d] - halfbd[d];
-      b[d] = ctr[d] + halfbd[d];
-      if (a[d] < bmin_[d]) a[d] = bmin_[d];
-      if (a[d] > bmax_[d]) a[d] = bmax_[d];
-      if (b[d] < bmin_[d]) b[d] = bmin_[d];
-      if (b[d] > bmax_[d]) b[d] = bmax_[d];
-    }
-    grid_index(a[0], a[1], a[2], c1);
-    grid_index(b[0], b[1], b[2], c2);
-  }
-  size_t addr(int i, int j, int k) const { return ((size_t)i * size_[1] + j) * size_[2] + k; }  // GridMap3D.h:129-130
   bool occupied(int i, int j, int k) const {  // GRD:239-283: out-of-range counts as occupied
     if (i < 0 || i >= size_[0] || j < 0 || j >= size_[1] || k < 0 || k >= size_[2]) return true;
     return occ_[addr(i, j, k)] != 0;
   }
-  void cube_center(int i, int j, int k, double p[3]) const {  // GRD:184-195
-    if (i < 0 || i >= size_[0] || j < 0 || j >= size_[1] || k < 0 || k >= size_[2]) { p[0] = p[1] = p[2] = 0.0; return; }
-    p[0] = (i + 0.5) * res_ + bmin_[0];
-    p[1] = (j + 0.5) * res_ + bmin_[1];
-    p[2] = (k + 0.5) * res_ + bmin_[2];
-  }
 
-  double res_ = 1.0;
-  double bmin_[3] = {0, 0, 0}, bmax_[3] = {0, 0, 0};
-  int size_[3] = {0, 0, 0};
   std::vector<unsigned char> occ_;
   size_t occupied_ = 0;
 };
+
+// The waypoint indices of generateTraj (plan_manager.cpp:132-140 and the loop header of :157): index_gap =
+// ceil(parlength / resolution), parlength /= 1.5 while index_gap >= path_size - 1, then index_gap, 2 index_gap, ... <
+// path_size - 1.  False for what the reference would not terminate on or would misbehave on.
+inline bool path_waypoints(size_t path_len, double grid_resolution, double traj_parlength, std::vector<size_t> &idx, int *index_gap) {
+  idx.clear();
+  if (path_len <= 2 || path_len > 0x7fffffffull || !(traj_parlength > 0.0) || !(grid_resolution > 0.0) ||
+      !std::isfinite(traj_parlength) || !std::isfinite(grid_resolution))
+    return false;
+  const double path_size = (double)path_len;
+  double temp_traj_parlength = traj_parlength;
+  // (in double until the loop is over: the reference's int cast of a ceil above INT_MAX is undefined, and such a gap is
+  // >= path_size - 1 anyway; each division by 1.5 shrinks it, so the loop ends, with a gap below path_size - 1)
+  double gap = std::ceil(temp_traj_parlength / grid_resolution);
+  while (gap >= path_size - 1.0) {
+    temp_traj_parlength /= 1.5;
+    gap = std::ceil(temp_traj_parlength / grid_resolution);
+  }
+  if (!(gap >= 1.0)) return false;   // the quotient underflowed to 0: `ind += 0` would never end
+  const size_t g = (size_t)gap;
+  for (size_t ind = g; ind < path_len - 1; ind += g) idx.push_back(ind);
+  if (index_gap) *index_gap = (int)g;
+  return true;
+}
 
 // ASCII PCD v0.7 with FIELDS x y z (src/plan_manager/pcds/map_*.pcd).  Returns false on any other layout.
 inline bool read_pcd_ascii(const char *path, std::vector<float> &xyz) {

@@ -34,6 +34,8 @@ EXPORTS = [
     "svsdf_last_launches", "svsdf_set_scale", "svsdf_get_scale",
     "svsdf_frontend_set_map", "svsdf_frontend_yaw_free", "svsdf_kernel_bfs", "svsdf_astar_successors",
     "svsdf_astar_params_default", "svsdf_astar_search", "svsdf_astar_nodes", "svsdf_debug_live_allocations",
+    "svsdf_map_build_device", "svsdf_map_device_get_info", "svsdf_map_device_cells", "svsdf_frontend_set_map_device",
+    "svsdf_set_points_from_map", "svsdf_map_device_points", "svsdf_path_waypoints",
 ]
 
 
@@ -120,6 +122,13 @@ class AstarResult(C.Structure):
 
 
 ASTAR_STATUS = ["FOUND", "EXHAUSTED", "LIMIT", "OUT_OF_MAP"]     # svsdf_astar_status
+
+
+class MapDeviceInfo(C.Structure):
+    """svsdf_map_device_info (include/svsdf_c.h)."""
+    _fields_ = [("struct_size", C.c_int), ("dims", C.c_int * 3), ("bmin", C.c_double * 3), ("bmax", C.c_double * 3),
+                ("resolution", C.c_double), ("sta_threshold", C.c_int), ("n_cloud", C.c_size_t), ("occupied", C.c_size_t),
+                ("gathered", C.c_size_t), ("build_ms", C.c_double), ("gather_ms", C.c_double)]
 
 
 class OutlineStats(C.Structure):
@@ -211,6 +220,14 @@ def lib():
                                       C.POINTER(C.c_int)]
     L.svsdf_frontend_set_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double]
     L.svsdf_frontend_yaw_free.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_size_t, _ip]
+    L.svsdf_map_build_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_double, C.c_int]
+    L.svsdf_map_device_get_info.argtypes = [C.c_void_p, C.POINTER(MapDeviceInfo)]
+    L.svsdf_map_device_cells.argtypes = [C.c_void_p, _u8p, C.c_size_t]
+    L.svsdf_frontend_set_map_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double]
+    L.svsdf_set_points_from_map.argtypes = [C.c_void_p, _dp, C.c_size_t, _dp, C.POINTER(C.c_size_t)]
+    L.svsdf_map_device_points.argtypes = [C.c_void_p, _dp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.svsdf_path_waypoints.argtypes = [C.c_size_t, C.c_double, C.c_double, C.POINTER(C.c_size_t), C.c_size_t,
+                                       C.POINTER(C.c_size_t), _ip]
     L.svsdf_kernel_bfs.argtypes = [C.c_ulonglong, C.c_int, C.c_double, _dp, _ip]
     L.svsdf_astar_successors.argtypes = [C.c_void_p, C.c_size_t, _ip, _dp, _u8p, _dp, _u8p]
     L.svsdf_astar_params_default.argtypes = [C.POINTER(AstarParams)]
@@ -277,6 +294,21 @@ def kernel_bfs(mask, kernel_count, father_yaw):
     if rc < 0:
         raise ValueError(f"svsdf_kernel_bfs({int(mask):#x}, {kernel_count}, {father_yaw!r}) rejected its arguments ({rc})")
     return (cy.value, ki.value) if rc else None
+
+
+def path_waypoints(path_len, grid_resolution, traj_parlength):
+    """The waypoint indices of generateTraj (plan_manager.cpp:132-140, 157; svsdf_path_waypoints, host only): returns
+    (indices int64 array, index_gap).  Raises ValueError for what the reference would not terminate on."""
+    n, gap = C.c_size_t(), C.c_int()
+    if int(path_len) < 0:
+        raise ValueError("path_waypoints: negative path_len")
+    args = (int(path_len), float(grid_resolution), float(traj_parlength))
+    if lib().svsdf_path_waypoints(*args, None, 0, C.byref(n), C.byref(gap)):
+        raise ValueError(f"svsdf_path_waypoints{args} rejected its arguments")
+    idx = np.zeros(max(n.value, 1), dtype=np.uintp)
+    if lib().svsdf_path_waypoints(*args, idx.ctypes.data_as(C.POINTER(C.c_size_t)), len(idx), C.byref(n), C.byref(gap)):
+        raise ValueError(f"svsdf_path_waypoints{args} rejected its arguments")
+    return idx[:n.value].astype(np.int64), gap.value
 
 
 def live_allocations():
@@ -741,6 +773,63 @@ class SvsdfContext:
         shape_kernels at the map's resolution, and the yaw-free table (svsdf_frontend_set_map)."""
         self._chk(self.L.svsdf_frontend_set_map(self.ctx, occupancy_map.h, int(kernel_size), int(kernel_count),
                                                 float(safemargin)), "svsdf_frontend_set_map")
+
+    # ---- the producer on the device (svsdf_map_build_device ...) ----
+    def map_build(self, cloud, resolution=1.0, sta_threshold=1):
+        """Build the device-resident occupancy map (svsdf_map_build_device).  cloud: (n, 3) float32 numpy array, or a
+        contiguous float32 torch tensor on the context's (first) device, passed by data_ptr()."""
+        if hasattr(cloud, "data_ptr"):
+            if str(cloud.dtype) != "torch.float32" or not cloud.is_contiguous() or cloud.numel() % 3:
+                raise ValueError("map_build: a device cloud must be a contiguous float32 tensor of n x 3 values")
+            ptr, n, on_dev = C.c_void_p(cloud.data_ptr() if cloud.numel() else None), cloud.numel() // 3, int(cloud.is_cuda)
+            keep = cloud
+        else:
+            keep = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 3)
+            ptr, n, on_dev = C.c_void_p(keep.ctypes.data if len(keep) else None), len(keep), 0
+        self._chk(self.L.svsdf_map_build_device(self.ctx, ptr, n, on_dev, float(resolution), int(sta_threshold)),
+                  "svsdf_map_build_device")
+        del keep
+
+    def map_info(self):
+        """svsdf_map_device_get_info as a dict: dims (tuple), bmin, bmax (arrays), resolution, sta_threshold, n_cloud,
+        occupied, gathered, build_ms, gather_ms."""
+        s = MapDeviceInfo()
+        s.struct_size = C.sizeof(MapDeviceInfo)
+        self._chk(self.L.svsdf_map_device_get_info(self.ctx, C.byref(s)), "svsdf_map_device_get_info")
+        out = {k: getattr(s, k) for k, _ in MapDeviceInfo._fields_ if k not in ("struct_size", "dims", "bmin", "bmax")}
+        out.update(dims=tuple(s.dims), bmin=np.array(list(s.bmin)), bmax=np.array(list(s.bmax)))
+        return out
+
+    def map_cells(self):
+        """The resident map's occupancy as a uint8 (X, Y, Z) array (svsdf_map_device_cells); dims below 1 count as 0."""
+        X, Y, Z = (max(0, d) for d in self.map_info()["dims"])
+        out = np.zeros((X, Y, Z), dtype=np.uint8)
+        self._chk(self.L.svsdf_map_device_cells(self.ctx, out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.size),
+                  "svsdf_map_device_cells")
+        return out
+
+    def frontend_set_map_resident(self, kernel_size, kernel_count, safemargin):
+        """frontend_set_map from the resident map, packed on the device (svsdf_frontend_set_map_device)."""
+        self._chk(self.L.svsdf_frontend_set_map_device(self.ctx, int(kernel_size), int(kernel_count), float(safemargin)),
+                  "svsdf_frontend_set_map_device")
+
+    def set_points_from_map(self, centres, halfbd):
+        """Gather the resident map's occupied voxels around `centres` (n, 3) -- boxes of half extents `halfbd` (3,), each
+        minus the previous centre's -- and make them the resident cloud (svsdf_set_points_from_map).  Returns the count."""
+        c = _f64(centres).reshape(-1, 3)
+        hb = _f64(halfbd).reshape(3)
+        n = C.c_size_t()
+        self._chk(self.L.svsdf_set_points_from_map(self.ctx, _p(c), len(c), _p(hb), C.byref(n)), "svsdf_set_points_from_map")
+        return int(n.value)
+
+    def map_points(self):
+        """The last gather in unified-voxel-id order, (n, 3) float64: what OccupancyMap.gather returns (svsdf_map_device_points)."""
+        n = C.c_size_t()
+        self._chk(self.L.svsdf_map_device_points(self.ctx, None, 0, C.byref(n)), "svsdf_map_device_points")
+        out = np.zeros((n.value, 3))
+        if n.value:
+            self._chk(self.L.svsdf_map_device_points(self.ctx, _p(out), n.value, C.byref(n)), "svsdf_map_device_points")
+        return out
 
     def yaw_free(self):
         """The yaw-free table as a uint64 (X, Y) array: bit k of [ix, iy] is set iff kernelConv<true>(k, (ix, iy, 0))

@@ -304,6 +304,62 @@ int svsdf_map_gather(const svsdf_map *map, const double *centres_xyz, size_t nce
 /* ASCII PCD v0.7, FIELDS x y z (src/plan_manager/pcds/map_*.pcd); xyz may be NULL to query n. */
 int svsdf_pcd_read_ascii(const char *path, float *xyz, size_t capacity, size_t *n);
 
+/* ---- query-point producer (device) ------------------------------------------------------------------- */
+/* The same producer with the map resident on the device: cloud -> occupancy grid -> front-end bitmap -> waypoint-box
+ * gather -> Morton-planned resident cloud, with no bulk data crossing back to the host.  Every step returns bit for bit
+ * what svsdf_map_create / svsdf_map_info / svsdf_frontend_set_map / svsdf_map_gather + svsdf_set_points return.  The
+ * resident map belongs to the context; a multi-device context keeps it on its first device, like the front end; a
+ * SVSDF_FLAG_HOST_ONLY context returns SVSDF_ERR_NO_DEVICE from every entry that takes one.
+ *
+ * svsdf_map_build_device replaces PCSmapManager::rcvGlobalMapHandler (src/map_manager/src/PCSmap_manager.cpp:88-210) with
+ * GridMap3D::createGridMap / isInMap / getGridIndex (src/map_manager/src/Gridmap3D.cpp:25-71, 137-177): bounds of the
+ * float32 cloud widened to double, from +-999999999; dims = ceil((bmax - bmin) / resolution); a voxel is occupied when it
+ * holds >= sta_threshold points.  xyz: n x 3 floats, in host memory (xyz_on_device = 0) or on the context's (first) device.
+ * It replaces any earlier resident map; a front-end map set from the earlier one stays until the next set-map call.
+ * n = 0 is accepted and reports what the host map reports (dims from the sentinel bounds, 0 cells); so is a flat cloud
+ * (an axis with bmax == bmin: 0 cells).  SVSDF_ERR_INVALID with a message: a NaN or infinite coordinate (a deliberate
+ * difference: the host builder casts floor(NaN) to int), a resolution that is not positive and finite, an axis or a product
+ * X * Y * Z above 2^31 - 1 (the unified voxel id is an int), n >= 2^32. */
+typedef struct svsdf_map_device_info {
+  int struct_size;                 /* sizeof(svsdf_map_device_info), set by the caller */
+  int dims[3];
+  double bmin[3], bmax[3], resolution;
+  int sta_threshold;
+  size_t n_cloud, occupied, gathered;   /* gathered: points of the last svsdf_set_points_from_map */
+  double build_ms, gather_ms;      /* host wall time of the two calls, synchronised */
+} svsdf_map_device_info;
+int svsdf_map_build_device(svsdf_ctx *ctx, const float *xyz, size_t n, int xyz_on_device, double resolution,
+                           int sta_threshold);
+int svsdf_map_device_get_info(const svsdf_ctx *ctx, svsdf_map_device_info *out);
+/* The occupancy bytes, occ_out[(i * Y + j) * Z + k] (GridMap3D.h:129-130); capacity >= X * Y * Z. */
+int svsdf_map_device_cells(const svsdf_ctx *ctx, unsigned char *occ_out, size_t capacity);
+/* svsdf_frontend_set_map (below) from the resident map: layer k = 0 is packed into the inflated bitmap
+ * (generateMapKernel2D, src/map_manager/include/map_manager/PCSmap_manager.h:81-108) on the device; everything after it is
+ * the same code.  Same limits and messages, under this entry's name, plus "no resident map". */
+int svsdf_frontend_set_map_device(svsdf_ctx *ctx, int kernel_size, int kernel_count, double safemargin);
+/* Replaces the waypoint loop around getPointsInAABBOutOfLastOne (src/plan_manager/src/plan_manager.cpp:156-175,
+ * PCSmap_manager.h:118-135, 184-219) with getGridCubeCenter / isIndexOccupied (Gridmap3D.cpp:184-195, 239-283), and the
+ * svsdf_set_points that follows: the occupied voxels of every centre's box that lie outside the previous centre's box,
+ * once each, ordered by unified voxel id, become the context's resident cloud through the planner of
+ * svsdf_set_points_device (a multi-device context distributes its stripes as there).  "Original index"
+ * (svsdf_shard_indices) is the position in that id-ordered list, exactly as after svsdf_map_gather + svsdf_set_points.
+ * ncentres = 0 or an empty result gives a valid empty cloud; the launch plan is reset as by any svsdf_set_points;
+ * svsdf_stats::setup_ms covers gather plus plan.  *count (may be NULL): the points gathered.  SVSDF_ERR_INVALID: no
+ * resident map, a non-finite centre or half extent (the reference indexes with floor(NaN)).  On a map of zero cells the
+ * result is empty (the host gather walks indices outside the grid there and returns (0, 0, 0) points). */
+int svsdf_set_points_from_map(svsdf_ctx *ctx, const double *centres_xyz, size_t ncentres, const double halfbd[3],
+                              size_t *count);
+/* The id-ordered list of the last gather, i.e. what svsdf_map_gather returns; out_xyz may be NULL to query the count. */
+int svsdf_map_device_points(const svsdf_ctx *ctx, double *out_xyz, size_t capacity, size_t *count);
+/* The waypoint indices of generateTraj (plan_manager.cpp:132-140 and the loop header of :157); pure host, no context.
+ * index_gap = ceil(traj_parlength / grid_resolution); while index_gap >= path_len - 1, traj_parlength /= 1.5 and again;
+ * indices index_gap, 2 index_gap, ... < path_len - 1.  idx_out may be NULL to query the count; index_gap may be NULL.
+ * The caller takes rows idx of the path (svsdf_astar_search's path_xyyaw: the z slot holds the yaw, as in the reference)
+ * as the centres of svsdf_set_points_from_map.  SVSDF_ERR_INVALID for what the reference would not terminate on or would
+ * misbehave on: path_len <= 2, traj_parlength <= 0, grid_resolution <= 0, non-finite values, capacity too small. */
+int svsdf_path_waypoints(size_t path_len, double grid_resolution, double traj_parlength, size_t *idx_out,
+                         size_t capacity, size_t *count, int *index_gap);
+
 /* ---- front end: yaw-kernel free-space table and batched A* successor test (device) ---------- */
 /* AstarPathSearcher::AstarGetSucc (src/planner_algorithm/include/planner_algorithm/front_end_Astar.hpp:192-241) tests
  * each of the 9 neighbours vi of a node in four steps: (1) isIndexValid(vi) && !isIndexOccupiedFlate(vi, 0)
