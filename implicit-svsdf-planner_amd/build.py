@@ -3,9 +3,10 @@
 hipcc cross-compiles for gfx950 without a GPU.  The .so is git-ignored but travels to the GPU
 box with the gpurun snapshot.
 
-Eight translation units, compiled in parallel and incrementally: the host layer in four (csrc/svsdf_pipeline.hip: one
+Nine translation units, compiled in parallel and incrementally: the host layer in five (csrc/svsdf_pipeline.hip: one
 device's pipeline + the shape-independent kernels; svsdf_group.hip: in-process multi-GPU; svsdf_capi.hip: the hot
-path's C ABI; svsdf_extras.hip: front end, map / mesh / outline helpers, L-BFGS driver) and
+path's C ABI; svsdf_extras.hip: front end, map / mesh / outline helpers, L-BFGS driver; svsdf_clearance.hip: the
+certified minimum clearance and its shape-independent kernels) and
 csrc/svsdf_shape_slice.hip four times (-DSVSDF_SLICE=0..3: the kernels specialised per shape id, shapes with
 id % 4 == slice).  A host-side edit recompiles one small unit; a kernel edit the pipeline unit and the slices.
 """
@@ -47,13 +48,13 @@ def _hipcc():
 
 
 def build(force=False, verbose=False, out=OUT, extra_flags=(), tag=""):
-    """Compile the five objects concurrently and link them.  `extra_flags` / `tag` / `out` make variant builds
+    """Compile the objects concurrently and link them.  `extra_flags` / `tag` / `out` make variant builds
     (tools/: e.g. extra_flags=["-DSVSDF_FAST_BUILD"], tag="fast", out=".../libsvsdf_hip_fast.so")."""
     if not force and not needs_build(out):
         return out
     hipcc = _hipcc()
     os.makedirs(OBJDIR, exist_ok=True)
-    units = [(h + tag, os.path.join(CSRC, f"svsdf_{h}.hip"), []) for h in ("pipeline", "group", "capi", "extras")]
+    units = [(h + tag, os.path.join(CSRC, f"svsdf_{h}.hip"), []) for h in ("pipeline", "group", "capi", "extras", "clearance")]
     units += [(f"slice{k}{tag}", os.path.join(CSRC, "svsdf_shape_slice.hip"), [f"-DSVSDF_SLICE={k}"]) for k in range(NSLICES)]
     procs = []
     objs_kept = []

@@ -1,0 +1,413 @@
+// svsdf_clearance.hip -- svsdf_min_clearance and svsdf_motion_bounds (include/svsdf_c.h): the host side of the
+// certified minimum-clearance search, and the shape-independent kernels of svsdf_clearance.hpp (SVSDF_CLR_TU).  The
+// shape-templated level kernels live in svsdf_shape_slice.hip behind launch_k_clr.
+#define SVSDF_CLR_TU
+#include "svsdf_ctx.hpp"
+
+using namespace svsdf;
+
+namespace svsdf_impl {
+namespace {
+
+// Bernstein coefficients of a polynomial given by its power coefficients a[0..n] on [0, 1]:
+//   b_j = sum_{i <= j} C(j, i) / C(n, i) a_i
+template <int n>
+void bernstein(const double *a, double *b) {
+  double cn[n + 1];
+  cn[0] = 1.0;
+  for (int i = 0; i < n; ++i) cn[i + 1] = cn[i] * (n - i) / (i + 1);
+  for (int j = 0; j <= n; ++j) {
+    double bj = 0.0, cji = 1.0;
+    for (int i = 0; i <= j; ++i) { bj += cji / cn[i] * a[i]; cji = cji * (j - i) / (i + 1); }
+    b[j] = bj;
+  }
+}
+
+// The Bernstein bound of upload_traj's exact cull on [ta, tb] (clamped to [0, S[N]]), made callable: per piece the velocity
+// quartics are shifted and scaled to the piece's part of the interval; their Bernstein coefficients bound them.  The planar
+// speed also has the degree-8 form vx^2 + vy^2, whose gap closes quadratically with the interval (the hypot of the two
+// axes' maxima is first order only: the axes peak at different ends).  Every bound is rounded up by what the shift can
+// have lost: `mag` bounds every intermediate of the shift, (k+1) |c_{k+1}| T^k summed.
+void motion_bounds_host(int N, const double *coeffs, const double *S, double ta, double tb, double out2[2]) {
+  const double td = S[N];
+  ta = std::min(std::max(ta, 0.0), td);
+  tb = std::min(std::max(tb, 0.0), td);
+  double vmax = 0.0, wmax = 0.0;
+  for (int i = 0; i < N; ++i) {
+    const double a = std::max(ta, S[i]) - S[i], b = std::min(tb, S[i + 1]) - S[i];   // local times in piece i
+    if (!(b >= a)) continue;
+    const double w = b - a, Ti = S[i + 1] - S[i];
+    double pw[3][5], bound[3], mag[3];
+    for (int d = 0; d < 3; ++d) {
+      double *p = pw[d];   // velocity in s: p[k] = (k+1) c_{k+1}
+      mag[d] = 0.0;
+      double tp = 1.0;
+      for (int k = 0; k < 5; ++k) {
+        p[k] = (k + 1) * coeffs[(size_t)d * 6 * N + 6 * i + k + 1];
+        mag[d] += std::fabs(p[k]) * tp;
+        tp *= Ti;
+      }
+      for (int j = 0; j < 4; ++j)          // Taylor shift s = a + s' (repeated synthetic division)
+        for (int k = 3; k >= j; --k) p[k] += a * p[k + 1];
+      double wp = 1.0;
+      for (int k = 0; k < 5; ++k) { p[k] *= wp; wp *= w; }   // s' = w u, u in [0, 1]
+      double bj[5];
+      bernstein<4>(p, bj);
+      bound[d] = 0.0;
+      for (int j = 0; j <= 4; ++j) bound[d] = std::max(bound[d], std::fabs(bj[j]));
+      bound[d] += 1e-13 * mag[d];
+    }
+    double q[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bq[9];
+    for (int k = 0; k < 5; ++k)
+      for (int l = 0; l < 5; ++l) q[k + l] += pw[0][k] * pw[0][l] + pw[1][k] * pw[1][l];
+    bernstein<8>(q, bq);
+    double v2 = 0.0;
+    for (int j = 0; j <= 8; ++j) v2 = std::max(v2, bq[j]);
+    const double m2 = mag[0] + mag[1];
+    const double v = std::min(std::hypot(bound[0], bound[1]), std::sqrt(v2 + 1e-12 * m2 * m2));
+    vmax = std::max(vmax, v);
+    wmax = std::max(wmax, bound[2]);
+  }
+  out2[0] = vmax * (1.0 + 1e-12);
+  out2[1] = wmax * (1.0 + 1e-12);
+}
+
+struct Events {   // the two events of device_ms
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
+struct Frontier {   // one chunk of a level's frontier: 2 * cap pairs
+  Buf<ClrPair> buf;
+  size_t n = 0;
+};
+
+constexpr double kInf = std::numeric_limits<double>::infinity();
+
+}  // namespace
+
+// The search on ONE device's stripe.  Arguments are validated by svsdf_min_clearance.
+int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, const svsdf_clearance_params &prm,
+                       svsdf_clearance_result *out) {
+  const char *const who = "svsdf_min_clearance";
+  const bool has_target = prm.target == prm.target;
+  *out = svsdf_clearance_result{};
+  out->lower = out->upper = kInf;
+  out->t_witness = 0.0;
+  out->point_index = -1;
+  if (ctx->P == 0) {   // nothing to be near to
+    out->status = has_target ? SVSDF_CLEARANCE_SAFE : SVSDF_CLEARANCE_CONVERGED;
+    return SVSDF_OK;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  Events ev;
+  HIPCHK(hipEventCreate(&ev.e0));
+  HIPCHK(hipEventCreate(&ev.e1));
+  HIPCHK(hipEventRecord(ev.e0, st));
+  {
+    // the upload of svsdf_debug_sdf_at (k_prep, piece-time mode); what it notes on the host for the evaluation it usually
+    // belongs to -- the launch record, the piece-time statistic, the persistent duration -- is put back
+    const int nl = ctx->n_launches;
+    const svsdf_launch_rec keep = ctx->launches[std::min(nl, SVSDF_LAUNCH_REC_CAP - 1)];
+    const int spt = ctx->stats_piece_time;
+    const double dur = ctx->traj_duration;
+    const bool have = ctx->have_duration;
+    const int rc = upload_traj_only(ctx, N, coeffs, T);
+    ctx->launches[std::min(nl, SVSDF_LAUNCH_REC_CAP - 1)] = keep;
+    ctx->n_launches = nl;
+    ctx->stats_piece_time = spt;
+    ctx->traj_duration = dur;
+    ctx->have_duration = have;
+    if (rc) return rc;
+  }
+  std::vector<double> S(N + 1, 0.0);
+  for (int i = 0; i < N; ++i) S[i + 1] = S[i] + T[i];
+  const double td = S[N];
+  size_t n0 = (size_t)std::max(1.0, std::ceil(td / 0.15));
+  if (td / (double)n0 > 0.15) ++n0;
+  const double w = td / (double)n0;
+  const unsigned P = (unsigned)ctx->P;
+  const unsigned ntiles = (P + kClrTile - 1) / kClrTile;
+  const size_t cap = prm.pair_capacity ? std::max<size_t>(prm.pair_capacity, kClrTile)
+                                       : std::min<size_t>(std::max<size_t>(2 * (size_t)P, 4096), (size_t)1 << 22);
+  if (cap > ((size_t)1 << 30)) return fail(ctx, SVSDF_ERR_INVALID, std::string(who) + ": pair_capacity above 2^30");
+  const unsigned long long budget = prm.max_evals ? prm.max_evals : 4ull * P * (unsigned long long)std::ceil(td / 0.15);
+
+  // level-0 motion bounds: the interval widened by 1e-4 s, as the cull widens 0.075 to 0.0751
+  std::vector<double> VW(2 * n0);
+  for (size_t j = 0; j < n0; ++j) {
+    const double m = clr_mid((unsigned)j, 0ull, 0, w, td), h = clr_half_width(w, 0);
+    double b2[2];
+    motion_bounds_host(N, coeffs, S.data(), m - h - 1e-4, m + h + 1e-4, b2);
+    VW[j] = b2[0];
+    VW[n0 + j] = b2[1];
+  }
+  const unsigned maxgrid = (unsigned)std::max(1, ctx->n_cu) * 8u;
+  Buf<double> d_vw;
+  Buf<Pose> d_mid;
+  Buf<long long> d_orig;
+  Buf<ClrTileCircle> d_tiles;
+  Buf<ClrPartial> d_partials;
+  Buf<ClrRecord> d_rec;
+  PinBuf<ClrRecord> h_rec;
+  Buf<unsigned long long> d_count;
+  Buf<ClrTilePair> d_tp, d_seed;
+  int rc = d_vw.alloc(ctx, 2 * n0);
+  if (rc == SVSDF_OK) rc = d_mid.alloc(ctx, n0);
+  if (rc == SVSDF_OK) rc = d_orig.alloc(ctx, P);
+  if (rc == SVSDF_OK) rc = d_tiles.alloc(ctx, ntiles);
+  if (rc == SVSDF_OK) rc = d_partials.alloc(ctx, maxgrid);
+  if (rc == SVSDF_OK) rc = d_rec.alloc(ctx, 1);
+  if (rc == SVSDF_OK) rc = h_rec.alloc(ctx, 1);
+  if (rc == SVSDF_OK) rc = d_count.alloc(ctx, 1);
+  if (rc == SVSDF_OK) rc = d_seed.alloc(ctx, 1);
+  if (rc) return rc;
+  const double *d_V = d_vw.get(), *d_W = d_vw.get() + n0;
+  HIPCHK_AS(who, hipMemcpyAsync(d_vw, VW.data(), 2 * n0 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK_AS(who, hipMemcpyAsync(d_orig, ctx->shard_idx.data(), (size_t)P * sizeof(long long), hipMemcpyHostToDevice, st));
+  const size_t traj_lds = (size_t)traj_lds_doubles(N) * sizeof(double);
+  hipLaunchKernelGGL(k_clr_tiles, dim3((ntiles + kClrBlock - 1) / kClrBlock), dim3(kClrBlock), 0, st, ctx->d_px.get(), ctx->d_py.get(), P,
+                     ntiles, d_tiles.get());
+  hipLaunchKernelGGL(k_clr_mid, dim3((unsigned)((n0 + 63) / 64)), dim3(64), traj_lds, st, ctx->d_traj.get(), w, (unsigned)n0, d_mid.get());
+  HIPCHK_AS(who, hipGetLastError());
+
+  // one launch's results on the host: reduce the blocks' partials, read the record
+  auto read_record = [&](unsigned grid) -> int {
+    hipLaunchKernelGGL(k_clr_reduce, dim3(1), dim3(kClrBlock), 0, st, d_partials.get(), grid, d_rec.get());
+    HIPCHK_AS(who, hipGetLastError());
+    HIPCHK_AS(who, hipMemcpyAsync(h_rec.get(), d_rec.get(), sizeof(ClrRecord), hipMemcpyDeviceToHost, st));
+    HIPCHK_AS(who, hipStreamSynchronize(st));
+    if (h_rec->overflow) return fail(ctx, SVSDF_ERR_INVALID, std::string(who) + ": internal error, a frontier buffer overflowed");
+    return SVSDF_OK;
+  };
+  const unsigned long long total_tp = (unsigned long long)ntiles * n0;
+  const unsigned broad_grid = (unsigned)std::min<unsigned long long>((total_tp + kClrBlock - 1) / kClrBlock, maxgrid);
+
+  // broad phase: the pair with the smallest cheap bound is evaluated first and gives the first upper
+  HIPCHK_AS(who, hipMemsetAsync(d_rec, 0, sizeof(ClrRecord), st));
+  hipLaunchKernelGGL(k_clr_broad, dim3(broad_grid), dim3(kClrBlock), 0, st, d_tiles.get(), ntiles, d_mid.get(), d_V, (unsigned)n0, w,
+                     ctx->r_bound, 0.0, (ClrTilePair *)nullptr, 0ull, (unsigned long long *)nullptr, d_partials.get());
+  if ((rc = read_record(broad_grid))) return rc;
+  ClrLaunch a{};
+  a.traj = ctx->d_traj; a.sp = ctx->sp; a.px = ctx->d_px; a.py = ctx->d_py; a.orig = d_orig; a.P = P; a.mid = d_mid;
+  a.V = d_V; a.W = d_W; a.w = w; a.dur = td; a.rec = d_rec; a.partials = d_partials;
+  auto launch = [&](unsigned grid) -> int {
+    if (!launch_k_clr(ctx->cfg.shape_id, grid, traj_lds, st, a))
+      return fail(ctx, SVSDF_ERR_INVALID, std::string(who) + ": shape not compiled into this build");
+    HIPCHK_AS(who, hipGetLastError());
+    return read_record(grid);
+  };
+  ClrBest best = clr_no_best();
+  unsigned long long evals = 0, pairs = 0;
+  {
+    const ClrTilePair seed{(unsigned)((unsigned long long)h_rec->best.idx / n0), (unsigned)((unsigned long long)h_rec->best.idx % n0)};
+    HIPCHK_AS(who, hipMemcpyAsync(d_seed, &seed, sizeof(seed), hipMemcpyHostToDevice, st));
+    HIPCHK_AS(who, hipMemsetAsync(d_rec, 0, sizeof(ClrRecord), st));
+    a.L = 0; a.tp = d_seed; a.n = 1; a.thr = 0.0; a.emit = 0; a.out = nullptr; a.out_cap = 0;
+    if ((rc = launch(1))) return rc;
+    best = h_rec->best;
+    evals += h_rec->evals;
+  }
+  // tiles whose cheap bound exceeds that upper cannot hold the minimum: the others are listed (count, then fill)
+  unsigned long long kept = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    HIPCHK_AS(who, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_clr_broad, dim3(broad_grid), dim3(kClrBlock), 0, st, d_tiles.get(), ntiles, d_mid.get(), d_V, (unsigned)n0, w,
+                       ctx->r_bound, best.f, pass ? d_tp.get() : (ClrTilePair *)nullptr, kept, d_count.get(), d_partials.get());
+    HIPCHK_AS(who, hipGetLastError());
+    unsigned long long c = 0;
+    HIPCHK_AS(who, hipMemcpyAsync(&c, d_count.get(), sizeof(c), hipMemcpyDeviceToHost, st));
+    HIPCHK_AS(who, hipStreamSynchronize(st));
+    if (pass == 0) {
+      kept = c;
+      if (kept > 0xffffffffull) return fail(ctx, SVSDF_ERR_INVALID, std::string(who) + ": too many (tile, interval) pairs");
+      if ((rc = d_tp.alloc(ctx, (size_t)kept))) return rc;
+    } else if (c != kept) {
+      return fail(ctx, SVSDF_ERR_INVALID, std::string(who) + ": internal error, the broad phase counted twice differently");
+    }
+  }
+
+  // the levels.  A frontier is a list of chunks of 2 * cap pairs; a launch takes <= cap pairs of one chunk and appends
+  // what they split into to the next frontier's last chunk, or to a fresh one when that has no room for all of them
+  std::vector<Frontier> cur, nxt, pool;
+  auto room = [&](size_t need) -> int {
+    if (!nxt.empty() && nxt.back().n + need <= 2 * cap) return SVSDF_OK;
+    Frontier f;
+    if (!pool.empty()) { f = std::move(pool.back()); pool.pop_back(); f.n = 0; }
+    else if (int r = f.buf.alloc(ctx, 2 * cap)) return r;
+    nxt.push_back(std::move(f));
+    return SVSDF_OK;
+  };
+  double settled = kInf, open = kInf;
+  int levels = 0, status = -1;
+  for (int L = 0;; ++L) {
+    unsigned long long todo = 0;   // evaluations of this level
+    if (L == 0) todo = kept * kClrTile;
+    else for (const Frontier &f : cur) todo += f.n;
+    if (L > 0 && (evals + todo > budget || L > kClrMaxLevel)) { status = SVSDF_CLEARANCE_BUDGET; break; }
+    const double thr = best.f - prm.eps;   // fixed before the level starts
+    ClrBest lbest = clr_no_best();
+    double lopen = kInf;
+    auto fold = [&](Frontier &dst) {
+      if (clr_better(h_rec->best, lbest)) lbest = h_rec->best;
+      settled = std::min(settled, h_rec->settled_min);
+      lopen = std::min(lopen, h_rec->open_min);
+      evals += h_rec->evals;
+      dst.n += (size_t)h_rec->out_count;
+    };
+    a.L = L; a.thr = thr; a.emit = 1;
+    if (L == 0) {
+      const size_t per = cap / kClrTile;   // >= 1
+      for (size_t off = 0; off < (size_t)kept; off += per) {
+        const size_t n = std::min(per, (size_t)kept - off);
+        if ((rc = room(2 * kClrTile * n))) return rc;
+        Frontier &dst = nxt.back();
+        HIPCHK_AS(who, hipMemsetAsync(d_rec, 0, sizeof(ClrRecord), st));
+        a.tp = d_tp.get() + off; a.n = (unsigned)n; a.out = dst.buf.get() + dst.n; a.out_cap = (unsigned)(2 * kClrTile * n);
+        if ((rc = launch((unsigned)std::min<size_t>((n + 3) / 4, maxgrid)))) return rc;
+        fold(dst);
+      }
+    } else {
+      pairs += todo;
+      for (Frontier &src : cur)
+        for (size_t off = 0; off < src.n; off += cap) {
+          const size_t n = std::min(cap, src.n - off);
+          if ((rc = room(2 * n))) return rc;
+          Frontier &dst = nxt.back();
+          HIPCHK_AS(who, hipMemsetAsync(d_rec, 0, sizeof(ClrRecord), st));
+          a.in = src.buf.get() + off; a.n = (unsigned)n; a.out = dst.buf.get() + dst.n; a.out_cap = (unsigned)(2 * n);
+          if ((rc = launch((unsigned)std::min<size_t>((n + kClrBlock - 1) / kClrBlock, maxgrid)))) return rc;
+          fold(dst);
+        }
+    }
+    ++levels;
+    if (clr_better(lbest, best)) best = lbest;
+    open = lopen;
+    for (Frontier &f : cur) pool.push_back(std::move(f));
+    cur.clear();
+    for (Frontier &f : nxt) { if (f.n) cur.push_back(std::move(f)); else pool.push_back(std::move(f)); }
+    nxt.clear();
+    if (has_target && std::min(settled, open) >= prm.target) { status = SVSDF_CLEARANCE_SAFE; break; }
+    if (has_target && best.f < prm.target) { status = SVSDF_CLEARANCE_UNSAFE; break; }
+    if (cur.empty()) { status = SVSDF_CLEARANCE_CONVERGED; break; }
+  }
+  double xy[2] = {0.0, 0.0};
+  HIPCHK_AS(who, hipMemcpyAsync(&xy[0], ctx->d_px.get() + best.pt, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK_AS(who, hipMemcpyAsync(&xy[1], ctx->d_py.get() + best.pt, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK_AS(who, hipEventRecord(ev.e1, st));
+  HIPCHK_AS(who, hipStreamSynchronize(st));
+  float ms = 0.0f;
+  HIPCHK_AS(who, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  out->status = status;
+  out->levels = levels;
+  out->upper = best.f;
+  out->lower = std::min(best.f, std::min(settled, open));   // every settled and every still-open bound
+  out->t_witness = best.t;
+  out->point_index = best.idx;
+  out->point_xy[0] = xy[0];
+  out->point_xy[1] = xy[1];
+  out->evals = evals;
+  out->pairs = pairs;
+  out->tile_pairs = total_tp;
+  out->tile_pairs_kept = kept;
+  out->device_ms = (double)ms;
+  return SVSDF_OK;
+}
+
+}  // namespace svsdf_impl
+
+using namespace svsdf_impl;
+
+extern "C" {
+
+void svsdf_clearance_params_default(svsdf_clearance_params *p) {
+  if (!p) return;
+  *p = svsdf_clearance_params{};
+  p->struct_size = sizeof(svsdf_clearance_params);
+  p->eps = 1e-3;
+  p->target = std::numeric_limits<double>::quiet_NaN();
+  p->max_evals = 0;
+  p->pair_capacity = 0;
+}
+
+int svsdf_motion_bounds(int N, const double *coeffs, const double *T, double ta, double tb, double out2[2]) {
+  if (!coeffs || !T || !out2 || N < 1 || N > kMaxPieces) return fail(nullptr, SVSDF_ERR_INVALID, "svsdf_motion_bounds: invalid argument");
+  if (ta != ta || tb != tb || tb < ta) return fail(nullptr, SVSDF_ERR_INVALID, "svsdf_motion_bounds: needs ta <= tb");
+  for (int i = 0; i < 18 * N; ++i)
+    if (!std::isfinite(coeffs[i])) return fail(nullptr, SVSDF_ERR_NONFINITE, "svsdf_motion_bounds: non-finite coefficient");
+  std::vector<double> S(N + 1, 0.0);
+  for (int i = 0; i < N; ++i) {
+    if (!std::isfinite(T[i])) return fail(nullptr, SVSDF_ERR_NONFINITE, "svsdf_motion_bounds: non-finite duration");
+    if (!(T[i] > 0.0)) return fail(nullptr, SVSDF_ERR_INVALID, "svsdf_motion_bounds: piece durations must be positive");
+    S[i + 1] = S[i] + T[i];
+  }
+  motion_bounds_host(N, coeffs, S.data(), ta, tb, out2);
+  return SVSDF_OK;
+}
+
+int svsdf_min_clearance(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, const svsdf_clearance_params *params,
+                        svsdf_clearance_result *out) {
+  if (!ctx || !coeffs || !T || !out) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: null argument");
+  svsdf_clearance_params prm;
+  svsdf_clearance_params_default(&prm);
+  if (params) {
+    if (params->struct_size != sizeof(svsdf_clearance_params))
+      return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: struct_size is not sizeof(svsdf_clearance_params)");
+    prm = *params;
+  }
+  if (!(prm.eps > 0.0) || !std::isfinite(prm.eps)) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: eps must be positive and finite");
+  if (ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "host-only context: no device entry points");
+  if (!ctx->points_set) return fail(ctx, SVSDF_ERR_NO_POINTS, "svsdf_set_points has not been called");
+  if (N < 1 || N > kMaxPieces) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: N out of range [1, 128]");
+  double td = 0.0;
+  for (int i = 0; i < N; ++i) td += T[i];
+  if (!std::isfinite(td)) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite duration");
+  for (int i = 0; i < 18 * N; ++i)
+    if (!std::isfinite(coeffs[i])) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite trajectory input");
+  for (int i = 0; i < N; ++i)
+    if (!(T[i] > 0.0)) return fail(ctx, SVSDF_ERR_INVALID, "piece durations must be positive");
+  if (!(td < 3 * 1e2))
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: total duration >= 300 s (the reference's stale-duration regime)");
+  svsdf_ctx *leaf = leaf_of(ctx);
+  if (ctx->scaled || leaf->scaled)
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: a scale schedule is set (the bound is the rigid one)");
+  if (!leaf->lipschitz_ok)
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: the shape SDF failed the context's Lipschitz self-check");
+  if (ctx->subs.empty()) return min_clearance_leaf(ctx, N, coeffs, T, prm, out);
+
+  // every stripe on its own device; the host combines
+  const size_t G = ctx->subs.size();
+  std::vector<svsdf_clearance_result> res(G);
+  size_t Ptot = 0;
+  for (svsdf_ctx *s : ctx->subs) Ptot += s->P;
+  const int rcg = group_run(ctx, [&](int k) -> int {
+    svsdf_clearance_params pk = prm;
+    if (prm.max_evals && Ptot)
+      pk.max_evals = std::max<unsigned long long>(1ull, (unsigned long long)std::ceil((double)prm.max_evals * (double)ctx->subs[k]->P / (double)Ptot));
+    return min_clearance_leaf(ctx->subs[k], N, coeffs, T, pk, &res[k]);
+  });
+  if (rcg) return rcg;
+  svsdf_clearance_result r = res[0];
+  bool any_budget = res[0].status == SVSDF_CLEARANCE_BUDGET;
+  for (size_t k = 1; k < G; ++k) {
+    const svsdf_clearance_result &q = res[k];
+    any_budget = any_budget || q.status == SVSDF_CLEARANCE_BUDGET;
+    const double lower = std::min(r.lower, q.lower);
+    const int levels = std::max(r.levels, q.levels);
+    const double ms = std::max(r.device_ms, q.device_ms);
+    const unsigned long long evals = r.evals + q.evals, pairs = r.pairs + q.pairs, tp = r.tile_pairs + q.tile_pairs,
+                             tk = r.tile_pairs_kept + q.tile_pairs_kept;
+    const bool take = q.point_index >= 0 && (r.point_index < 0 || q.upper < r.upper || (q.upper == r.upper && q.point_index < r.point_index));
+    if (take) r = q;
+    r.lower = lower; r.levels = levels; r.device_ms = ms; r.evals = evals; r.pairs = pairs; r.tile_pairs = tp; r.tile_pairs_kept = tk;
+  }
+  const bool has_target = prm.target == prm.target;
+  if (has_target && r.lower >= prm.target) r.status = SVSDF_CLEARANCE_SAFE;
+  else if (has_target && r.upper < prm.target) r.status = SVSDF_CLEARANCE_UNSAFE;
+  else r.status = any_budget ? SVSDF_CLEARANCE_BUDGET : SVSDF_CLEARANCE_CONVERGED;
+  *out = r;
+  return SVSDF_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,253 @@
+// svsdf_clearance.hpp -- device side of svsdf_min_clearance: a level-synchronous branch and bound over (point, time interval)
+// pairs that brackets
+//   c* = min over p in the resident cloud, t in [0, sum T] of getSDFAtTimeStamp<false>(p, t)      (SWM:741-750)
+// (DESIGN.md §4e).  The bound is the one the exact cull rests on (svsdf_pipeline.hip upload_traj, scan_layer1): for a
+// 1-Lipschitz shape SDF, a pose x(t) that moves at most V per second and turns at most W per second on an interval of half
+// width h around m,
+//   sdf(p, t) >= sdf(p, m) - h (V + W |p - x(m)|)            for every t of the interval.
+// Intervals: [0, sum T] is cut into n0 equal intervals of width w <= 0.15 s (level 0); interval (j, k) of level L is the
+// k-th of the 2^L equal parts of level-0 interval j, its midpoint (j + (2k + 1) / 2^(L+1)) w.  V and W are the level-0
+// interval's (the host's Bernstein bounds), inherited by every descendant.
+// Kernels:
+//   k_clr_tiles    bounding circle of every run of 64 consecutive points of the resident SoA cloud
+//   k_clr_mid      pose at every level-0 midpoint (pose_at: what every SDF-at-time evaluation inlines)
+//   k_clr_broad    the cheap bound |c_tile - x(m)| - r_tile - h V - r_bound of every (tile, interval): its minimum, or the
+//                  list of the pairs a threshold keeps
+//   k_clr_level0<SHAPE>  one wave per kept (tile, interval): transform + shape SDF against the midpoint's pose
+//   k_clr_level<SHAPE>   one lane per (point, interval) pair of a deeper level: pose_at + sdf_from_pose
+//   k_clr_reduce   fixed-order reduction of the blocks' partial results into one record the host reads
+// A level's pruning threshold is a kernel argument, fixed by the host before the level starts; the only atomics are the
+// integer slot counters of the compaction, so the SET of pairs a level emits, and with it every reported number, does not
+// depend on the order the lanes ran in.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "svsdf_kernels.hpp"
+
+namespace svsdf {
+
+constexpr int kClrBlock = 256;
+constexpr int kClrTile = 64;        // points per tile = lanes of a wave
+constexpr int kClrMaxLevel = 44;    // h = w / 2^45 ~ 2e-15 s: below that an interval is a single double
+
+struct ClrPair { unsigned pt, j; unsigned long long k; };   // shard-local point, level-0 interval, index within it
+struct ClrTileCircle { double cx, cy, r; };
+struct ClrTilePair { unsigned tile, j; };
+// The best evaluation so far: smallest value, then smallest original point index, then smallest time.
+struct ClrBest { double f; long long idx; double t; unsigned pt; unsigned pad_; };
+struct ClrPartial { ClrBest best; double settled_min, open_min; unsigned long long evals; };
+// What the host reads per launch.  out_count / overflow are written by the level kernels (integer atomics), the rest by k_clr_reduce.
+struct ClrRecord { ClrBest best; double settled_min, open_min; unsigned long long evals, out_count; unsigned overflow, pad_; };
+
+__host__ __device__ __forceinline__ bool clr_better(const ClrBest &a, const ClrBest &b) {
+  return a.f < b.f || (a.f == b.f && (a.idx < b.idx || (a.idx == b.idx && a.t < b.t)));
+}
+__host__ __device__ __forceinline__ ClrBest clr_no_best() {
+  ClrBest b;
+  b.f = __builtin_huge_val(); b.idx = 0x7fffffffffffffffll; b.t = __builtin_huge_val(); b.pt = 0u; b.pad_ = 0u;
+  return b;
+}
+// midpoint and half width of interval (j, k) of level L; every kernel and the host use this one expression
+__host__ __device__ __forceinline__ double clr_half_width(double w, int L) { return __builtin_ldexp(w, -(L + 1)); }
+__host__ __device__ __forceinline__ double clr_mid(unsigned j, unsigned long long k, int L, double w, double dur) {
+  const double frac = __builtin_ldexp((double)(2ull * k + 1ull), -(L + 1));   // exact: 2k + 1 < 2^(L+1) <= 2^45
+  const double m = ((double)j + frac) * w;
+  return m < dur ? m : dur;
+}
+// the lane's lower bound over its interval: the allowance convention of the exact cull (upload_traj)
+__device__ __forceinline__ double clr_lower(double f, double h, double V, double W, double D) {
+  return f - (h * (V + W * D) * (1.0 + 1e-9) + 1e-9);
+}
+
+// block-wide fixed-order reduction of the lanes' partials; thread 0 writes the block's
+__device__ __forceinline__ void clr_block_reduce(ClrPartial mine, ClrPartial *__restrict__ out) {
+  __shared__ ClrPartial s_part[kClrBlock];
+  s_part[threadIdx.x] = mine;
+  __syncthreads();
+  for (int s = kClrBlock / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s && (int)threadIdx.x + s < (int)blockDim.x) {
+      ClrPartial a = s_part[threadIdx.x];
+      const ClrPartial b = s_part[threadIdx.x + s];
+      if (clr_better(b.best, a.best)) a.best = b.best;
+      a.settled_min = b.settled_min < a.settled_min ? b.settled_min : a.settled_min;
+      a.open_min = b.open_min < a.open_min ? b.open_min : a.open_min;
+      a.evals += b.evals;
+      s_part[threadIdx.x] = a;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[blockIdx.x] = s_part[0];
+}
+__device__ __forceinline__ ClrPartial clr_no_partial() {
+  ClrPartial p;
+  p.best = clr_no_best(); p.settled_min = __builtin_huge_val(); p.open_min = __builtin_huge_val(); p.evals = 0ull;
+  return p;
+}
+
+// A pair's verdict against the level's threshold: settled (its bound joins the settled minimum) or split into its halves.
+// `emit == 0` (the seed evaluation): values only.
+__device__ __forceinline__ void clr_settle_or_split(ClrPartial &mine, double lb, double thr, int emit, unsigned pt, unsigned j,
+                                                    unsigned long long k, ClrPair *__restrict__ out, unsigned out_cap,
+                                                    ClrRecord *__restrict__ rec) {
+  if (!emit) return;
+  if (lb >= thr) {
+    mine.settled_min = lb < mine.settled_min ? lb : mine.settled_min;
+    return;
+  }
+  mine.open_min = lb < mine.open_min ? lb : mine.open_min;
+  const unsigned long long slot = atomicAdd(&rec->out_count, 2ull);
+  if (slot + 2ull > (unsigned long long)out_cap) { rec->overflow = 1u; return; }   // (the host sizes the buffer for every pair splitting)
+  ClrPair c;
+  c.pt = pt; c.j = j; c.k = 2ull * k;
+  out[slot] = c;
+  c.k = 2ull * k + 1ull;
+  out[slot + 1] = c;
+}
+
+// Level 0: wave v of the launch takes (tile, interval) pair tp[v], lane l the tile's point l.  The value is
+// sdf_from_pose against the midpoint's pose from k_clr_mid, i.e. pose_at's pose: bit for bit sdf_at(p, m).
+template <int SHAPE>
+__global__ void __launch_bounds__(kClrBlock)
+k_clr_level0(ShapeParams sp, const double *__restrict__ px_, const double *__restrict__ py_, const long long *__restrict__ orig,
+             unsigned P, const Pose *__restrict__ mid, const double *__restrict__ V_, const double *__restrict__ W_, double w,
+             double dur, const ClrTilePair *__restrict__ tp, unsigned ntp, double thr, int emit, ClrPair *__restrict__ out,
+             unsigned out_cap, ClrRecord *__restrict__ rec, ClrPartial *__restrict__ partials) {
+  ClrPartial mine = clr_no_partial();
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = kClrBlock / 64;
+  const double h = clr_half_width(w, 0);
+  for (unsigned v = blockIdx.x * waves + wave; v < ntp; v += gridDim.x * waves) {
+    const ClrTilePair q = tp[v];
+    const unsigned pt = q.tile * (unsigned)kClrTile + lane;
+    if (pt >= P) continue;
+    const Pose p = mid[q.j];
+    const double px = px_[pt], py = py_[pt];
+    const double f = sdf_from_pose<SHAPE>(sp, p, px, py);
+    ClrBest b;
+    b.f = f; b.idx = orig[pt]; b.t = clr_mid(q.j, 0ull, 0, w, dur); b.pt = pt; b.pad_ = 0u;
+    if (clr_better(b, mine.best)) mine.best = b;
+    mine.evals += 1ull;
+    const double dx = px - p.x, dy = py - p.y;
+    const double lb = clr_lower(f, h, V_[q.j], W_[q.j], sqrt(dx * dx + dy * dy));
+    clr_settle_or_split(mine, lb, thr, emit, pt, q.j, 0ull, out, out_cap, rec);
+  }
+  clr_block_reduce(mine, partials);
+}
+
+// Level L >= 1: lane per pair, the evaluation of k_debug_sdf_at (pose_at, sdf_from_pose, the context's piece-time mode).
+template <int SHAPE>
+__global__ void __launch_bounds__(kClrBlock)
+k_clr_level(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__restrict__ px_, const double *__restrict__ py_,
+            const long long *__restrict__ orig, const double *__restrict__ V_, const double *__restrict__ W_, double w, int L,
+            const ClrPair *__restrict__ in, unsigned n, double thr, ClrPair *__restrict__ out, unsigned out_cap,
+            ClrRecord *__restrict__ rec, ClrPartial *__restrict__ partials) {
+  extern __shared__ double clr_lds[];
+  const TrajL tr = stage_traj(trg, clr_lds);
+  ClrPartial mine = clr_no_partial();
+  const double h = clr_half_width(w, L);
+  PieceCache pc = piece_cache_init();
+  for (unsigned i = blockIdx.x * kClrBlock + threadIdx.x; i < n; i += gridDim.x * kClrBlock) {
+    const ClrPair q = in[i];
+    const double t = clr_mid(q.j, q.k, L, w, tr.dur);
+    const Pose p = pose_at(tr, t, pc);
+    const double px = px_[q.pt], py = py_[q.pt];
+    const double f = sdf_from_pose<SHAPE>(sp, p, px, py);
+    ClrBest b;
+    b.f = f; b.idx = orig[q.pt]; b.t = t; b.pt = q.pt; b.pad_ = 0u;
+    if (clr_better(b, mine.best)) mine.best = b;
+    mine.evals += 1ull;
+    const double dx = px - p.x, dy = py - p.y;
+    const double lb = clr_lower(f, h, V_[q.j], W_[q.j], sqrt(dx * dx + dy * dy));
+    clr_settle_or_split(mine, lb, thr, 1, q.pt, q.j, q.k, out, out_cap, rec);
+  }
+  clr_block_reduce(mine, partials);
+}
+
+#ifdef SVSDF_CLR_TU   // shape-independent kernels: compiled once, by svsdf_clearance.hip
+
+// Bounding circle of points [64 i, 64 i + 64) of the cloud: centre of their box, radius the largest distance to it, rounded up.
+__global__ void __launch_bounds__(kClrBlock)
+k_clr_tiles(const double *__restrict__ px, const double *__restrict__ py, unsigned P, unsigned ntiles, ClrTileCircle *__restrict__ tiles) {
+  const unsigned i = blockIdx.x * kClrBlock + threadIdx.x;
+  if (i >= ntiles) return;
+  const unsigned p0 = i * (unsigned)kClrTile, p1 = (p0 + (unsigned)kClrTile < P) ? p0 + (unsigned)kClrTile : P;
+  double x0 = px[p0], x1 = x0, y0 = py[p0], y1 = y0;
+  for (unsigned p = p0 + 1; p < p1; ++p) {
+    const double x = px[p], y = py[p];
+    x0 = x < x0 ? x : x0; x1 = x > x1 ? x : x1;
+    y0 = y < y0 ? y : y0; y1 = y > y1 ? y : y1;
+  }
+  ClrTileCircle c;
+  c.cx = 0.5 * (x0 + x1); c.cy = 0.5 * (y0 + y1);
+  double r2 = 0.0;
+  for (unsigned p = p0; p < p1; ++p) {
+    const double dx = px[p] - c.cx, dy = py[p] - c.cy;
+    const double d2 = dx * dx + dy * dy;
+    r2 = d2 > r2 ? d2 : r2;
+  }
+  c.r = sqrt(r2) * (1.0 + 1e-12);
+  tiles[i] = c;
+}
+
+// Pose at the midpoint of every level-0 interval.  One wave per block, like k_debug_sdf_at.
+__global__ void __launch_bounds__(64)
+k_clr_mid(const TrajDev *__restrict__ trg, double w, unsigned n0, Pose *__restrict__ mid) {
+  extern __shared__ double clr_mid_lds[];
+  const TrajL tr = stage_traj(trg, clr_mid_lds);
+  const unsigned j = blockIdx.x * 64u + threadIdx.x;
+  if (j >= n0) return;
+  PieceCache pc = piece_cache_init();
+  mid[j] = pose_at(tr, clr_mid(j, 0ull, 0, w, tr.dur), pc);
+}
+
+// cheap bound of (tile, interval): every point of the tile is at least this far outside the shape during the interval
+__device__ __forceinline__ double clr_cheap(const ClrTileCircle c, const Pose p, double h, double V, double r_bound) {
+  const double dx = c.cx - p.x, dy = c.cy - p.y;
+  return sqrt(dx * dx + dy * dy) * (1.0 - 1e-12) - c.r - r_bound - (h * V * (1.0 + 1e-9) + 1e-9);
+}
+
+// list == null, count == null: the minimum of the cheap bound (ties: the smallest pair index) as block partials.
+// count != null: the pairs with cheap <= thr are counted, and written to `list` when there is one (cap entries).
+__global__ void __launch_bounds__(kClrBlock)
+k_clr_broad(const ClrTileCircle *__restrict__ tiles, unsigned ntiles, const Pose *__restrict__ mid, const double *__restrict__ V_,
+            unsigned n0, double w, double r_bound, double thr, ClrTilePair *__restrict__ list, unsigned long long cap,
+            unsigned long long *__restrict__ count, ClrPartial *__restrict__ partials) {
+  ClrPartial mine = clr_no_partial();
+  const double h = clr_half_width(w, 0);
+  const unsigned long long total = (unsigned long long)ntiles * n0;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * kClrBlock + threadIdx.x; i < total; i += (unsigned long long)gridDim.x * kClrBlock) {
+    const unsigned tile = (unsigned)(i / n0), j = (unsigned)(i % n0);
+    const double cheap = clr_cheap(tiles[tile], mid[j], h, V_[j], r_bound);
+    if (count) {
+      if (cheap <= thr) {
+        const unsigned long long slot = atomicAdd(count, 1ull);
+        if (list && slot < cap) { ClrTilePair q; q.tile = tile; q.j = j; list[slot] = q; }
+      }
+    } else {
+      ClrBest b;
+      b.f = cheap; b.idx = (long long)i; b.t = 0.0; b.pt = 0u; b.pad_ = 0u;
+      if (clr_better(b, mine.best)) mine.best = b;
+    }
+  }
+  if (!count) clr_block_reduce(mine, partials);
+}
+
+// one block: the blocks' partials in index order -> the record (out_count / overflow are the level kernels')
+__global__ void __launch_bounds__(kClrBlock)
+k_clr_reduce(const ClrPartial *__restrict__ partials, unsigned n, ClrRecord *__restrict__ rec) {
+  __shared__ ClrPartial s_one[1];
+  ClrPartial mine = clr_no_partial();
+  for (unsigned i = threadIdx.x; i < n; i += kClrBlock) {
+    const ClrPartial b = partials[i];
+    if (clr_better(b.best, mine.best)) mine.best = b.best;
+    mine.settled_min = b.settled_min < mine.settled_min ? b.settled_min : mine.settled_min;
+    mine.open_min = b.open_min < mine.open_min ? b.open_min : mine.open_min;
+    mine.evals += b.evals;
+  }
+  clr_block_reduce(mine, s_one);   // (blockIdx.x == 0: lands in s_one[0])
+  __syncthreads();
+  if (threadIdx.x == 0) { rec->best = s_one[0].best; rec->settled_min = s_one[0].settled_min; rec->open_min = s_one[0].open_min; rec->evals = s_one[0].evals; }
+}
+
+#endif  // SVSDF_CLR_TU
+
+}  // namespace svsdf

@@ -467,6 +467,10 @@ long long sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, int n);
 long long sqrt_mismatches(svsdf_ctx *ctx, const double *x, size_t n, int flavour);
 int debug_sdf_at(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, size_t n, const double *pxy, const double *t, double *out8);
 int site_stats(svsdf_ctx *ctx, unsigned long long out[20]);
+int upload_traj_only(svsdf_ctx *ctx, int N, const double *coeffs, const double *T);   // upload_traj, as svsdf_debug_sdf_at runs it
+// ---- svsdf_clearance.hip
+int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, const svsdf_clearance_params &prm,
+                       svsdf_clearance_result *out);
 // ---- svsdf_group.hip
 int upload_group_device(svsdf_ctx *ctx, const double *d_xyz, size_t P);
 int group_run(svsdf_ctx *ctx, const std::function<int(int)> &f);

@@ -169,6 +169,10 @@ bool launch_k_astar(int shape, hipStream_t st, ShapeParams sp, const FrontMapDev
   shape = svsdf_impl::compiled_shape(shape);
   SVSDF_SLICE_DISPATCH(launch_k_astar, st, sp, fm, a, slice)
 }
+bool launch_k_clr(int shape, unsigned grid, size_t lds, hipStream_t st, const ClrLaunch &a) {
+  shape = svsdf_impl::compiled_shape(shape);
+  SVSDF_SLICE_DISPATCH(launch_k_clr, grid, lds, st, a)
+}
 void launch_k_pack_kernel_rows(hipStream_t st, const unsigned char *map, int ks, int count, unsigned long long *rows) {
   hipLaunchKernelGGL(k_pack_kernel_rows, dim3((unsigned)((ks * count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, map, ks,
                      count, rows);
@@ -1253,6 +1257,8 @@ int debug_sdf_at(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, s
   HIPCHK_AS("svsdf_debug_sdf_at", hipStreamSynchronize(ctx->stream));
   return SVSDF_OK;
 }
+
+int upload_traj_only(svsdf_ctx *ctx, int N, const double *coeffs, const double *T) { return upload_traj(ctx, N, coeffs, T); }
 
 // mismatch count of the kernels' inlined sincos against the device library's (svsdf_debug_sincos_mismatches)
 long long sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, int n) {

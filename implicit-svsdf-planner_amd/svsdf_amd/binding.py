@@ -36,6 +36,7 @@ EXPORTS = [
     "svsdf_astar_params_default", "svsdf_astar_search", "svsdf_astar_nodes", "svsdf_debug_live_allocations",
     "svsdf_map_build_device", "svsdf_map_device_get_info", "svsdf_map_device_cells", "svsdf_frontend_set_map_device",
     "svsdf_set_points_from_map", "svsdf_map_device_points", "svsdf_path_waypoints",
+    "svsdf_clearance_params_default", "svsdf_min_clearance", "svsdf_motion_bounds",
 ]
 
 
@@ -129,6 +130,23 @@ class MapDeviceInfo(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("dims", C.c_int * 3), ("bmin", C.c_double * 3), ("bmax", C.c_double * 3),
                 ("resolution", C.c_double), ("sta_threshold", C.c_int), ("n_cloud", C.c_size_t), ("occupied", C.c_size_t),
                 ("gathered", C.c_size_t), ("build_ms", C.c_double), ("gather_ms", C.c_double)]
+
+
+class ClearanceParams(C.Structure):
+    """svsdf_clearance_params (include/svsdf_c.h)."""
+    _fields_ = [("struct_size", C.c_size_t), ("eps", C.c_double), ("target", C.c_double), ("max_evals", C.c_ulonglong),
+                ("pair_capacity", C.c_size_t)]
+
+
+class ClearanceResult(C.Structure):
+    """svsdf_clearance_result (include/svsdf_c.h)."""
+    _fields_ = [("status", C.c_int), ("levels", C.c_int), ("lower", C.c_double), ("upper", C.c_double),
+                ("t_witness", C.c_double), ("point_index", C.c_longlong), ("point_xy", C.c_double * 2),
+                ("evals", C.c_ulonglong), ("pairs", C.c_ulonglong), ("tile_pairs", C.c_ulonglong),
+                ("tile_pairs_kept", C.c_ulonglong), ("device_ms", C.c_double)]
+
+
+CLEARANCE_STATUS = ["CONVERGED", "SAFE", "UNSAFE", "BUDGET"]     # SVSDF_CLEARANCE_*
 
 
 class OutlineStats(C.Structure):
@@ -243,6 +261,10 @@ def lib():
                                       C.POINTER(OutlineStats)]
     L.svsdf_outline_extrude.argtypes = [_dp, _ip, C.c_size_t, C.c_double, C.c_double, C.c_int, _dp, C.c_size_t,
                                         C.POINTER(C.c_size_t), _ip, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.svsdf_clearance_params_default.argtypes = [C.POINTER(ClearanceParams)]
+    L.svsdf_clearance_params_default.restype = None
+    L.svsdf_min_clearance.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(ClearanceParams), C.POINTER(ClearanceResult)]
+    L.svsdf_motion_bounds.argtypes = [C.c_int, _dp, _dp, C.c_double, C.c_double, _dp]
     if hasattr(L, "svsdf_mesh_section"):   # (the guards: absent only from A/B libraries built from older commits, tools/build_ref_variant.sh)
         L.svsdf_mesh_section.argtypes = [_dp, C.c_size_t, _ip, C.c_size_t, C.c_double, _dp, C.c_size_t, C.POINTER(C.c_size_t), _ip,
                                          C.c_size_t, C.POINTER(C.c_size_t)]
@@ -309,6 +331,18 @@ def path_waypoints(path_len, grid_resolution, traj_parlength):
     if lib().svsdf_path_waypoints(*args, idx.ctypes.data_as(C.POINTER(C.c_size_t)), len(idx), C.byref(n), C.byref(gap)):
         raise ValueError(f"svsdf_path_waypoints{args} rejected its arguments")
     return idx[:n.value].astype(np.int64), gap.value
+
+
+def motion_bounds(coeffs, T, ta, tb):
+    """Rigorous (max planar speed, max |yaw rate|) of the trajectory on [ta, tb] clipped to [0, sum T]
+    (svsdf_motion_bounds; host only).  coeffs (6N, 3), T (N,)."""
+    T = _f64(T)
+    cm = _colmajor(coeffs)
+    o = np.zeros(2)
+    rc = lib().svsdf_motion_bounds(len(T), _p(cm), _p(T), float(ta), float(tb), _p(o))
+    if rc:
+        raise SvsdfError(f"svsdf_motion_bounds failed ({rc}): " + lib().svsdf_last_error_string(None).decode())
+    return float(o[0]), float(o[1])
 
 
 def live_allocations():
@@ -908,6 +942,27 @@ class SvsdfContext:
         tt = _f64(t).ravel().copy()
         out = np.zeros((len(tt), 8))
         self._chk(self.L.svsdf_debug_sdf_at(self.ctx, len(T), _p(cm), _p(T), len(tt), _p(xy), _p(tt), _p(out)), "svsdf_debug_sdf_at")
+        return out
+
+    def min_clearance(self, coeffs, T, eps=1e-3, target=None, max_evals=0, pair_capacity=0, struct_size=None):
+        """Certified bracket lower <= c* <= upper on the minimum over the resident cloud and over [0, sum T] of the
+        SDF-at-time, with a witness (svsdf_min_clearance).  Returns the fields of svsdf_clearance_result as a dict
+        (status as one of CLEARANCE_STATUS, point_xy as a tuple).  target=None: no target."""
+        T = _f64(T)
+        cm = _colmajor(coeffs)
+        prm = ClearanceParams()
+        self.L.svsdf_clearance_params_default(C.byref(prm))
+        prm.eps = float(eps)
+        if target is not None:
+            prm.target = float(target)
+        prm.max_evals, prm.pair_capacity = int(max_evals), int(pair_capacity)
+        if struct_size is not None:
+            prm.struct_size = int(struct_size)
+        res = ClearanceResult()
+        self._chk(self.L.svsdf_min_clearance(self.ctx, len(T), _p(cm), _p(T), C.byref(prm), C.byref(res)), "svsdf_min_clearance")
+        out = {k: getattr(res, k) for k, _ in ClearanceResult._fields_}
+        out["status"] = CLEARANCE_STATUS[res.status]
+        out["point_xy"] = (res.point_xy[0], res.point_xy[1])
         return out
 
     def sincos_mismatches(self, lo, hi, n):

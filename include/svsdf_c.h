@@ -526,6 +526,60 @@ int svsdf_outline_extrude(const double *xy, const int *loop_sizes, size_t n_loop
                           double *V_out, size_t capacity_verts, size_t *n_verts, int *F_out, size_t capacity_tris,
                           size_t *n_tris);
 
+/* ---- certified minimum clearance (device) -----------------------------------------------------
+ * A certified bracket lower <= c* <= upper on
+ *   c* = min over p in the resident cloud, t in [0, sum T] of getSDFAtTimeStamp<false>(p, t)      (SWM:741-750),
+ * the GLOBAL minimum over the whole cloud and the whole duration -- not the per-point local minimum the hot path's
+ * argmin solve returns (svsdf_query_points: one basin per point, the one its seed fell into) and not the 51 sampled poses
+ * of checkSubSWCollision (SWM:1171-1211).  With it a witness: sdf_at(point, t_witness) == upper, a value the device
+ * evaluated, reproducible with svsdf_debug_sdf_at.  The search is a level-synchronous branch and bound over (point, time
+ * interval) pairs on the device: [0, sum T] is cut into equal intervals at most 0.15 s wide; a pair of half width h
+ * around m is bounded below by sdf_at(p, m) - h (V + W |p - x(m)|) with V, W the interval's svsdf_motion_bounds (the shape
+ * SDF is 1-Lipschitz: svsdf_shape_selfcheck); a pair whose bound reaches upper - eps is settled, any other is halved.
+ * Runs of 64 consecutive resident points are first tested as a whole by their bounding circle (tile_pairs /
+ * tile_pairs_kept).  Results do not depend on pair_capacity, and two calls return identical structs except device_ms.
+ * The call uploads the trajectory like svsdf_debug_sdf_at (same piece-time mode) and leaves the resident cloud, the
+ * launch plan, svsdf_last_stats and the bits of every later evaluation as they were.  A multi-device context searches
+ * every stripe on its own device; the host takes the smallest lower, the smallest upper with its witness (ties: the
+ * smaller original index) and sums the counters (levels, device_ms: the largest).
+ * Returns SVSDF_ERR_NO_POINTS without a resident cloud, SVSDF_ERR_NO_DEVICE on a host-only context,
+ * SVSDF_ERR_NONFINITE for a non-finite trajectory, SVSDF_ERR_INVALID with a message for a bad N, eps or struct_size, a
+ * scale schedule in force (svsdf_set_scale: the bound is the rigid one), a total duration >= 300 s (the reference's
+ * stale-duration regime, SWM:376-385) and a context whose Lipschitz self-check failed.  An empty resident cloud gives
+ * lower = upper = +infinity and point_index = -1. */
+typedef struct svsdf_clearance_params {
+  size_t struct_size;            /* sizeof(svsdf_clearance_params) */
+  double eps;                    /* > 0, finite: converged when upper - lower <= eps (default 1e-3) */
+  double target;                 /* NaN (default): none.  Otherwise the search stops after the first level at which
+                                    lower >= target (SAFE) or upper < target (UNSAFE) */
+  unsigned long long max_evals;  /* budget of SDF-at-time evaluations: a level that would exceed it is not started.
+                                    0: 4 * P * ceil(sum T / 0.15).  Level 0 always runs.  A multi-device context gives
+                                    every stripe its share by point count */
+  size_t pair_capacity;          /* pairs one launch evaluates; a frontier buffer holds twice as many (every pair may
+                                    split).  0: by cloud size.  Values below 64 (one tile) are raised to 64.  A larger
+                                    frontier is processed in slices of the same level */
+} svsdf_clearance_params;
+enum { SVSDF_CLEARANCE_CONVERGED = 0, SVSDF_CLEARANCE_SAFE = 1, SVSDF_CLEARANCE_UNSAFE = 2, SVSDF_CLEARANCE_BUDGET = 3 };
+typedef struct svsdf_clearance_result {
+  int status, levels;            /* levels: levels evaluated, level 0 included */
+  double lower, upper;           /* lower <= c* <= upper, always, whatever the status */
+  double t_witness; long long point_index; double point_xy[2];   /* sdf_at(point, t_witness) == upper; index into the svsdf_set_points array */
+  unsigned long long evals, pairs, tile_pairs, tile_pairs_kept;  /* SDF-at-time evaluations (the seed tile's included);
+                                    (point, interval) pairs of levels >= 1; (tile, level-0 interval) pairs, and those
+                                    the broad phase kept */
+  double device_ms;              /* HIP-event time from the trajectory upload to the last level */
+} svsdf_clearance_result;
+void svsdf_clearance_params_default(svsdf_clearance_params *p);
+int svsdf_min_clearance(svsdf_ctx *ctx, int N, const double *coeffs, const double *T,
+                        const svsdf_clearance_params *params /* may be NULL */, svsdf_clearance_result *out);
+/* Host only, no context: rigorous bounds out2 = {max planar speed, max |yaw rate|} of the trajectory on
+ * [ta, tb] intersected with [0, sum T] (coeffs, T as for svsdf_eval_penalty).  Per piece, the quartic velocity
+ * polynomials restricted to the interval lie in the convex hull of their Bernstein coefficients (the bound of the exact
+ * cull); the planar speed is the smaller of hypot(max |vx|, max |vy|) and the square root of the largest Bernstein
+ * coefficient of the degree-8 polynomial vx^2 + vy^2.  Rounded up.  SVSDF_ERR_INVALID: N outside [1, SVSDF_MAX_PIECES],
+ * tb < ta, a NaN bound of the interval, a non-positive duration; SVSDF_ERR_NONFINITE: a non-finite coefficient or duration. */
+int svsdf_motion_bounds(int N, const double *coeffs, const double *T, double ta, double tb, double out2[2]);
+
 /* ---- host-side MINCO helpers (MNC:397-655) ------------------------------------------------------- */
 /* waypoints inPs: 3 x (N-1) col-major; out coeffs (6N) x 3 col-major. */
 int svsdf_minco_coeffs(const double head_state[9], const double tail_state[9], int N,
