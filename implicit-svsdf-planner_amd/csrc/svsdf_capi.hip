@@ -387,8 +387,7 @@ int svsdf_query_points(svsdf_ctx *ctx, int N, const double *coeffs, const double
     if (!rcg) merge_stats(ctx);
     return rcg;
   }
-  if (ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "host-only context: no device entry points");
-  if (!ctx->points_set) return fail(ctx, SVSDF_ERR_NO_POINTS, "svsdf_set_points has not been called");
+  if (int rc = require_resident(ctx)) return rc;
   if (ctx->P == 0) return SVSDF_OK;
   int rc = evaluate_points(ctx, N, coeffs, T, /*allow_cull=*/false, /*with_partial=*/false);  // per-point outputs need every solve
   if (rc) return rc;

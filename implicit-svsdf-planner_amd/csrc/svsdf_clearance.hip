@@ -9,69 +9,6 @@ using namespace svsdf;
 namespace svsdf_impl {
 namespace {
 
-// Bernstein coefficients of a polynomial given by its power coefficients a[0..n] on [0, 1]:
-//   b_j = sum_{i <= j} C(j, i) / C(n, i) a_i
-template <int n>
-void bernstein(const double *a, double *b) {
-  double cn[n + 1];
-  cn[0] = 1.0;
-  for (int i = 0; i < n; ++i) cn[i + 1] = cn[i] * (n - i) / (i + 1);
-  for (int j = 0; j <= n; ++j) {
-    double bj = 0.0, cji = 1.0;
-    for (int i = 0; i <= j; ++i) { bj += cji / cn[i] * a[i]; cji = cji * (j - i) / (i + 1); }
-    b[j] = bj;
-  }
-}
-
-// The Bernstein bound of upload_traj's exact cull on [ta, tb] (clamped to [0, S[N]]), made callable: per piece the velocity
-// quartics are shifted and scaled to the piece's part of the interval; their Bernstein coefficients bound them.  The planar
-// speed also has the degree-8 form vx^2 + vy^2, whose gap closes quadratically with the interval (the hypot of the two
-// axes' maxima is first order only: the axes peak at different ends).  Every bound is rounded up by what the shift can
-// have lost: `mag` bounds every intermediate of the shift, (k+1) |c_{k+1}| T^k summed.
-void motion_bounds_host(int N, const double *coeffs, const double *S, double ta, double tb, double out2[2]) {
-  const double td = S[N];
-  ta = std::min(std::max(ta, 0.0), td);
-  tb = std::min(std::max(tb, 0.0), td);
-  double vmax = 0.0, wmax = 0.0;
-  for (int i = 0; i < N; ++i) {
-    const double a = std::max(ta, S[i]) - S[i], b = std::min(tb, S[i + 1]) - S[i];   // local times in piece i
-    if (!(b >= a)) continue;
-    const double w = b - a, Ti = S[i + 1] - S[i];
-    double pw[3][5], bound[3], mag[3];
-    for (int d = 0; d < 3; ++d) {
-      double *p = pw[d];   // velocity in s: p[k] = (k+1) c_{k+1}
-      mag[d] = 0.0;
-      double tp = 1.0;
-      for (int k = 0; k < 5; ++k) {
-        p[k] = (k + 1) * coeffs[(size_t)d * 6 * N + 6 * i + k + 1];
-        mag[d] += std::fabs(p[k]) * tp;
-        tp *= Ti;
-      }
-      for (int j = 0; j < 4; ++j)          // Taylor shift s = a + s' (repeated synthetic division)
-        for (int k = 3; k >= j; --k) p[k] += a * p[k + 1];
-      double wp = 1.0;
-      for (int k = 0; k < 5; ++k) { p[k] *= wp; wp *= w; }   // s' = w u, u in [0, 1]
-      double bj[5];
-      bernstein<4>(p, bj);
-      bound[d] = 0.0;
-      for (int j = 0; j <= 4; ++j) bound[d] = std::max(bound[d], std::fabs(bj[j]));
-      bound[d] += 1e-13 * mag[d];
-    }
-    double q[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bq[9];
-    for (int k = 0; k < 5; ++k)
-      for (int l = 0; l < 5; ++l) q[k + l] += pw[0][k] * pw[0][l] + pw[1][k] * pw[1][l];
-    bernstein<8>(q, bq);
-    double v2 = 0.0;
-    for (int j = 0; j <= 8; ++j) v2 = std::max(v2, bq[j]);
-    const double m2 = mag[0] + mag[1];
-    const double v = std::min(std::hypot(bound[0], bound[1]), std::sqrt(v2 + 1e-12 * m2 * m2));
-    vmax = std::max(vmax, v);
-    wmax = std::max(wmax, bound[2]);
-  }
-  out2[0] = vmax * (1.0 + 1e-12);
-  out2[1] = wmax * (1.0 + 1e-12);
-}
-
 struct Events {   // the two events of device_ms
   hipEvent_t e0 = nullptr, e1 = nullptr;
   ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
@@ -105,24 +42,8 @@ int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double
   HIPCHK(hipEventCreate(&ev.e0));
   HIPCHK(hipEventCreate(&ev.e1));
   HIPCHK(hipEventRecord(ev.e0, st));
-  {
-    // the upload of svsdf_debug_sdf_at (k_prep, piece-time mode); what it notes on the host for the evaluation it usually
-    // belongs to -- the launch record, the piece-time statistic, the persistent duration -- is put back
-    const int nl = ctx->n_launches;
-    const svsdf_launch_rec keep = ctx->launches[std::min(nl, SVSDF_LAUNCH_REC_CAP - 1)];
-    const int spt = ctx->stats_piece_time;
-    const double dur = ctx->traj_duration;
-    const bool have = ctx->have_duration;
-    const int rc = upload_traj_only(ctx, N, coeffs, T);
-    ctx->launches[std::min(nl, SVSDF_LAUNCH_REC_CAP - 1)] = keep;
-    ctx->n_launches = nl;
-    ctx->stats_piece_time = spt;
-    ctx->traj_duration = dur;
-    ctx->have_duration = have;
-    if (rc) return rc;
-  }
-  std::vector<double> S(N + 1, 0.0);
-  for (int i = 0; i < N; ++i) S[i + 1] = S[i] + T[i];
+  if (int rc = upload_traj(ctx, N, coeffs, T, TrajUse::probe)) return rc;   // (k_prep, piece-time mode: as an evaluation's)
+  const std::vector<double> S = svsdf_traj::prefix_sums(N, T);
   const double td = S[N];
   size_t n0 = (size_t)std::max(1.0, std::ceil(td / 0.15));
   if (td / (double)n0 > 0.15) ++n0;
@@ -139,7 +60,7 @@ int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double
   for (size_t j = 0; j < n0; ++j) {
     const double m = clr_mid((unsigned)j, 0ull, 0, w, td), h = clr_half_width(w, 0);
     double b2[2];
-    motion_bounds_host(N, coeffs, S.data(), m - h - 1e-4, m + h + 1e-4, b2);
+    svsdf_traj::motion_bounds(N, coeffs, S.data(), m - h - 1e-4, m + h + 1e-4, b2);
     VW[j] = b2[0];
     VW[n0 + j] = b2[1];
   }
@@ -332,17 +253,11 @@ void svsdf_clearance_params_default(svsdf_clearance_params *p) {
 }
 
 int svsdf_motion_bounds(int N, const double *coeffs, const double *T, double ta, double tb, double out2[2]) {
-  if (!coeffs || !T || !out2 || N < 1 || N > kMaxPieces) return fail(nullptr, SVSDF_ERR_INVALID, "svsdf_motion_bounds: invalid argument");
+  if (!coeffs || !T || !out2) return fail(nullptr, SVSDF_ERR_INVALID, "svsdf_motion_bounds: null argument");
   if (ta != ta || tb != tb || tb < ta) return fail(nullptr, SVSDF_ERR_INVALID, "svsdf_motion_bounds: needs ta <= tb");
-  for (int i = 0; i < 18 * N; ++i)
-    if (!std::isfinite(coeffs[i])) return fail(nullptr, SVSDF_ERR_NONFINITE, "svsdf_motion_bounds: non-finite coefficient");
-  std::vector<double> S(N + 1, 0.0);
-  for (int i = 0; i < N; ++i) {
-    if (!std::isfinite(T[i])) return fail(nullptr, SVSDF_ERR_NONFINITE, "svsdf_motion_bounds: non-finite duration");
-    if (!(T[i] > 0.0)) return fail(nullptr, SVSDF_ERR_INVALID, "svsdf_motion_bounds: piece durations must be positive");
-    S[i + 1] = S[i] + T[i];
-  }
-  motion_bounds_host(N, coeffs, S.data(), ta, tb, out2);
+  const svsdf_traj::TrajCheck chk = svsdf_traj::check_traj(N, coeffs, T);
+  if (chk.code) return fail(nullptr, chk.code, std::string("svsdf_motion_bounds: ") + chk.reason);
+  svsdf_traj::motion_bounds(N, coeffs, svsdf_traj::prefix_sums(N, T).data(), ta, tb, out2);
   return SVSDF_OK;
 }
 
@@ -357,17 +272,10 @@ int svsdf_min_clearance(svsdf_ctx *ctx, int N, const double *coeffs, const doubl
     prm = *params;
   }
   if (!(prm.eps > 0.0) || !std::isfinite(prm.eps)) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: eps must be positive and finite");
-  if (ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "host-only context: no device entry points");
-  if (!ctx->points_set) return fail(ctx, SVSDF_ERR_NO_POINTS, "svsdf_set_points has not been called");
-  if (N < 1 || N > kMaxPieces) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: N out of range [1, 128]");
-  double td = 0.0;
-  for (int i = 0; i < N; ++i) td += T[i];
-  if (!std::isfinite(td)) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite duration");
-  for (int i = 0; i < 18 * N; ++i)
-    if (!std::isfinite(coeffs[i])) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite trajectory input");
-  for (int i = 0; i < N; ++i)
-    if (!(T[i] > 0.0)) return fail(ctx, SVSDF_ERR_INVALID, "piece durations must be positive");
-  if (!(td < 3 * 1e2))
+  if (int rc = require_resident(ctx)) return rc;
+  const svsdf_traj::TrajCheck chk = svsdf_traj::check_traj(N, coeffs, T);
+  if (chk.code) return fail(ctx, chk.code, std::string("svsdf_min_clearance: ") + chk.reason);
+  if (!(chk.td < 3 * 1e2))
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: total duration >= 300 s (the reference's stale-duration regime)");
   svsdf_ctx *leaf = leaf_of(ctx);
   if (ctx->scaled || leaf->scaled)

@@ -35,6 +35,7 @@
 #include "svsdf_launch.hpp"
 #include "svsdf_layout.hpp"
 #include "svsdf_minco.hpp"
+#include "svsdf_traj_host.hpp"
 
 // One host thread per device of an in-process multi-GPU context.
 struct Worker {
@@ -376,6 +377,12 @@ extern const char *kShapeNames[SVSDF_SHAPE_COUNT];
 
 // ---- The prologue of a device entry point.  A multi-device context owns no device state: its first stripe's context stands in.
 inline svsdf_ctx *leaf_of(svsdf_ctx *c) { return c->subs.empty() ? c : c->subs[0]; }
+// What an entry that reads the resident cloud needs: a device, and svsdf_set_points before it.
+inline int require_resident(svsdf_ctx *ctx) {
+  if (ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "host-only context: no device entry points");
+  if (!ctx->points_set) return fail(ctx, SVSDF_ERR_NO_POINTS, "svsdf_set_points has not been called");
+  return SVSDF_OK;
+}
 // `body(leaf)` on a context that has a device; the leaf's error string becomes the group's when the body fails on it.
 // `name`: the entry point, for "<name>: no device context".
 template <typename Body>
@@ -467,7 +474,12 @@ long long sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, int n);
 long long sqrt_mismatches(svsdf_ctx *ctx, const double *x, size_t n, int flavour);
 int debug_sdf_at(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, size_t n, const double *pxy, const double *t, double *out8);
 int site_stats(svsdf_ctx *ctx, unsigned long long out[20]);
-int upload_traj_only(svsdf_ctx *ctx, int N, const double *coeffs, const double *T);   // upload_traj, as svsdf_debug_sdf_at runs it
+// What a trajectory upload is for.  An evaluation (svsdf_debug_sdf_at included) updates the persistent traj_duration, notes
+// the piece-time statistic and records the k_prep launch.  A probe (svsdf_min_clearance, which has refused 300 s and more)
+// takes the trajectory's own duration and leaves those three alone; it still overwrites N, K, the cull fields (slack_max,
+// cull_ok), piece_time_mode, ltab_mode, the staging block and the device tables -- every evaluation rewrites all of these.
+enum class TrajUse { evaluation, probe };
+int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, TrajUse use, bool clear_nonfinite = false);
 // ---- svsdf_clearance.hip
 int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, const svsdf_clearance_params &prm,
                        svsdf_clearance_result *out);

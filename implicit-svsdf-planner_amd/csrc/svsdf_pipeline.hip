@@ -383,127 +383,42 @@ void launch_classify(svsdf_ctx *ctx, hipStream_t st, int b) {
   debug_sync(st, "k_classify", b, 0);
 }
 
-// Upload (coeffs, T), update traj_duration like SweptVolumeManager::updateTraj (SWM:376-385),
-// build the layer-1 time grid exactly like the reference's accumulating loop (SWM:567).
-int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bool clear_nonfinite = false) {
-  if (N < 1 || N > kMaxPieces) return fail(ctx, SVSDF_ERR_INVALID, "N out of range [1, 128]");
-  double td = 0.0;
-  for (int i = 0; i < N; ++i) td += T[i];  // Trajectory::getTotalDuration (TRJ:410-419)
-  if (!(td == td) || std::isinf(td)) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite duration");
-  // forwardT (BEO:213-226) only produces positive durations and Trajectory asserts t_max > 0; a non-positive
-  // piece would leave the scan table empty
-  for (int i = 0; i < N; ++i)
-    if (!(T[i] > 0.0)) return fail(ctx, SVSDF_ERR_INVALID, "piece durations must be positive");
-  if (td < 3 * 1e2 || !ctx->have_duration) {
-    ctx->traj_duration = td;
-    ctx->have_duration = true;
-  }
-  const double dur = ctx->traj_duration;
-  size_t K = 0;
-  for (double t = 0.0; t <= dur; t += 0.15) ++K;
+// Upload (coeffs, T) and build what the kernels read beside them (svsdf_traj_host.hpp): the layer-1 time grid, the exact
+// cull's table, the piece-time mode; then k_prep.  An evaluation updates traj_duration first (SWM:376-385).
+int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, TrajUse use, bool clear_nonfinite) {
+  const svsdf_traj::TrajCheck chk = svsdf_traj::check_traj(N, coeffs, T);
+  if (chk.code) return fail(ctx, chk.code, chk.reason);
+  if (use == TrajUse::evaluation) svsdf_traj::update_duration(chk.td, ctx->traj_duration, ctx->have_duration);
+  const double td = chk.td, dur = (use == TrajUse::probe) ? td : ctx->traj_duration;
+  if (!(dur / 0.15 < 16002.0)) return fail(ctx, SVSDF_ERR_INVALID, "trajectory duration out of range for the scan table");
+  const size_t room = TrajInput::doubles(N, (int)svsdf_traj::scan_times_room(dur));   // (sized before the grid is counted: it is written as it is counted)
+  if (room > ctx->in.cap)
+    if (int rc = ctx->in.reserve(ctx, room + 4096)) return rc;
+  double *const tk = TrajInputRW(ctx->in.h, N, 0).tk();   // (tk starts behind coeffs and T, whatever K)
+  const size_t K = svsdf_traj::scan_times(dur, tk);
   if (K < 1 || K > 16000) return fail(ctx, SVSDF_ERR_INVALID, "trajectory duration out of range for the scan table");
-  const size_t need = TrajInput::doubles(N, (int)K);
-  if (need > ctx->in.cap) {
-    int rc = ctx->in.reserve(ctx, need + 4096);
-    if (rc) return rc;
-  }
   if (K > ctx->pose_cap) {
-    int rc = ctx->d_pose.alloc(ctx, K + 1024);
-    if (rc) return rc;
-    rc = ctx->d_chunks.alloc(ctx, 2 * ((K + 1024) / kChunk + 2));   // chunk records, then the anchor table (ChunkAnchor, k_prep)
-    if (rc) return rc;
+    if (int rc = ctx->d_pose.alloc(ctx, K + 1024)) return rc;
+    // chunk records, then the anchor table (ChunkAnchor, k_prep)
+    if (int rc = ctx->d_chunks.alloc(ctx, 2 * ((K + 1024) / kChunk + 2))) return rc;
     ctx->pose_cap = K + 1024;
   }
   const TrajInputRW in(ctx->in.h, N, (int)K);
   std::memcpy(in.coeffs(), coeffs, sizeof(double) * 18 * N);
   std::memcpy(in.T(), T, sizeof(double) * N);
-  double *const tk = in.tk();
-  {
-    size_t k = 0;
-    for (double t = 0.0; t <= dur; t += 0.15) tk[k++] = t;
-  }
-  for (const double *v = in.coeffs(); v < tk; ++v)   // coeffs and T
-    if (!std::isfinite(*v)) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite trajectory input");
-  {
-    // Exact cull (k_solve, main points): a point is skipped when  min_c(|p - c_c| - rb_c - slack_c) > safety_hor.
-    // Chunk c holds the table times t_k0 .. t_k1; every t of [t_k0 - h, t_k1 + h] lies within h of one of them
-    // (h = half the table spacing; the last chunk also covers (t_last, dur]), so |x(t) - x(t_k)| <= V_c * h with
-    // V_c a rigorous bound of the planar speed on that interval: the quartic velocity polynomials lie in the
-    // convex hull of their Bernstein coefficients on the sub-interval.  Then sdf(t) >= |p - x(t)| - R_shape >=
-    // |p - c_c| - rb_c - V_c * h for every continuous t, whatever local minimum the reference's search returns,
-    // and smoothedL1 (BEO:316-340) is inactive.  Only in the regular regime (traj_duration not stale).
-    const size_t nch = (size_t)TrajInput::chunk_count((int)K);
-    double *slack = in.slack();
-    double *rot = in.rot();   // W_c * h: yaw-rate allowance of the value-based second cull (scan_layer1)
-    ctx->slack_max = 0.0;
-    ctx->cull_ok = (td == dur) && K >= 1;
-    std::vector<double> S(N + 1, 0.0);
-    for (int i = 0; i < N; ++i) S[i + 1] = S[i] + T[i];
-    for (size_t c = 0; c < nch; ++c) {
-      slack[c] = std::numeric_limits<double>::infinity();
-      rot[c] = std::numeric_limits<double>::infinity();
-      if (!ctx->cull_ok) continue;
-      const size_t k0 = c * kChunk, k1 = std::min(k0 + kChunk, K) - 1;
-      const double h = (c + 1 == nch) ? std::max(0.0751, dur - tk[k1]) : 0.0751;
-      const double ta = std::max(0.0, tk[k0] - h), tb = std::min(td, tk[k1] + h);
-      double v2 = 0.0, wmax = 0.0;
-      for (int i = 0; i < N; ++i) {
-        const double a = std::max(ta, S[i]) - S[i], b = std::min(tb, S[i + 1]) - S[i];  // local times in piece i
-        if (!(b >= a)) continue;
-        const double w = b - a;
-        double bound[3] = {0.0, 0.0, 0.0};
-        for (int d = 0; d < 3; ++d) {
-          double p[5];  // velocity in s: p[k] = (k+1) c_{k+1}
-          for (int k = 0; k < 5; ++k) p[k] = (k + 1) * coeffs[(size_t)d * 6 * N + 6 * i + k + 1];
-          for (int j = 0; j < 4; ++j)          // Taylor shift s = a + s' (repeated synthetic division)
-            for (int k = 3; k >= j; --k) p[k] += a * p[k + 1];
-          double wp = 1.0;
-          for (int k = 0; k < 5; ++k) { p[k] *= wp; wp *= w; }   // s' = w u, u in [0, 1]
-          static const double binom4[5] = {1, 4, 6, 4, 1};
-          for (int j = 0; j <= 4; ++j) {
-            double bj = 0.0, cjq = 1.0;  // C(j, q)
-            for (int q = 0; q <= j; ++q) { bj += cjq / binom4[q] * p[q]; cjq = cjq * (j - q) / (q + 1); }
-            bound[d] = std::max(bound[d], std::fabs(bj));
-          }
-        }
-        v2 = std::max(v2, std::hypot(bound[0], bound[1]));
-        wmax = std::max(wmax, bound[2]);
-      }
-      const double sl = v2 * (1.0 + 1e-9) * h + 1e-9;
-      if (std::isfinite(sl)) { slack[c] = sl; ctx->slack_max = std::max(ctx->slack_max, sl); }
-      const double rl = wmax * (1.0 + 1e-9) * h + 1e-12;
-      if (std::isfinite(rl)) rot[c] = rl;
-    }
-  }
-  {
-    // Piece-local time: the reference subtracts the durations one after the other from t
-    // (TRJ:498-516); t - (T_0 + ... + T_{i-1}) in one subtraction is the same number only when every operation
-    // involved is exact.  That is guaranteed when all durations are coarse dyadic numbers (multiples of 2^-20 below
-    // 2^20, e.g. the 2.5 s of every BASELINE config): then all partial sums and all differences with any t < 2^30
-    // are exact in both forms.  Otherwise (an optimiser's durations are generic doubles) the faithful chain runs.
-    bool coarse = dur < 1073741824.0;
-    double tmin = std::numeric_limits<double>::infinity();
-    for (int i = 0; i < N; ++i) {
-      const double v = std::ldexp(T[i], 20);
-      coarse = coarse && T[i] < 1048576.0 && v == std::floor(v);
-      tmin = std::min(tmin, T[i]);
-    }
-    const int f = ctx->cfg.flags;
-    int mode = (f & SVSDF_FLAG_EXACT_PIECE_TIME) ? 1 : (f & SVSDF_FLAG_FAST_PIECE_TIME) ? 0 : (coarse ? 0 : 1);
-    if (mode == 1 && !(tmin >= 1e-6)) mode = 2;
-    ctx->piece_time_mode = mode;
-    ctx->stats_piece_time = mode;
-  }
-  ctx->N = N;
-  ctx->K = (int)K;
-  HIPCHK(hipMemcpyAsync(ctx->in.d, ctx->in.h, need * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const std::vector<double> S = svsdf_traj::prefix_sums(N, T);
+  const svsdf_traj::CullTable cull = svsdf_traj::cull_table(N, coeffs, S.data(), tk, K, dur, td, (size_t)kChunk, in.slack(), in.rot());
+  ctx->slack_max = cull.slack_max; ctx->cull_ok = cull.ok;
+  ctx->piece_time_mode = svsdf_traj::piece_time_mode(ctx->cfg.flags, N, T, dur);
+  if (use == TrajUse::evaluation) ctx->stats_piece_time = ctx->piece_time_mode;
+  ctx->N = N; ctx->K = (int)K;
+  HIPCHK(hipMemcpyAsync(ctx->in.d, ctx->in.h, TrajInput::doubles(N, (int)K) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   const size_t lds = (size_t)traj_lds_doubles(N) * sizeof(double);
   // one block of 1024 threads (round 6; 256 before): a pose per thread for the ~ 600 poses of a reference-scale trajectory
   // instead of three one after the other, and four waves per SIMD to hide the chain's latencies behind
-  hipLaunchKernelGGL(k_prep, dim3(1), dim3(1024), lds, ctx->stream, ctx->in.d, N, dur, (int)K,
-                     ctx->piece_time_mode, ctx->d_traj,
+  hipLaunchKernelGGL(k_prep, dim3(1), dim3(1024), lds, ctx->stream, ctx->in.d, N, dur, (int)K, ctx->piece_time_mode, ctx->d_traj,
                      ctx->d_pose, ctx->d_chunks, ctx->r_bound, ctx->d_ctl, ctx->nbatch, clear_nonfinite ? ctx->d_nonfinite : nullptr);
-  (void)record_launch(ctx, SVSDF_KERNEL_PREP, -1, 1, 1024, lds, (long long)K, 0);
+  if (use == TrajUse::evaluation) (void)record_launch(ctx, SVSDF_KERNEL_PREP, -1, 1, 1024, lds, (long long)K, 0);
   ctx->ltab_mode = 0;   // (the tables on the device belong to the previous trajectory: build_layer_tables)
   return SVSDF_OK;
 }
@@ -597,16 +512,21 @@ static void begin_evaluation(svsdf_ctx *ctx) {
   ctx->stats = svsdf_stats{}; ctx->stats.points = ctx->P;
   reset_launches(ctx);
 }
+// The main points of batch b as a query set: the resident cloud itself, one query per point.
+static QuerySet main_queries(const svsdf_ctx *ctx, int b) {
+  QuerySet qm{};   // (no stride, no count on the device, no list)
+  qm.qx = ctx->d_px; qm.qy = ctx->d_py; qm.count_fixed = ctx->bcount[b]; qm.base = ctx->bstart[b]; qm.n_outer = 1;
+  return qm;
+}
 // Enqueue the device pipeline up to the per-point results of getTrueSDFofSweptVolume (res_*).
 // No host synchronisation: batches run on their own streams, joined back onto ctx->stream.
 int enqueue_queries(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, bool allow_cull) {
-  if (ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "host-only context: no device entry points");
-  if (!ctx->points_set) return fail(ctx, SVSDF_ERR_NO_POINTS, "svsdf_set_points has not been called");
+  if (int rc = require_resident(ctx)) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   begin_evaluation(ctx);
   const size_t e_begin = next_event(ctx);
   (void)hipEventRecord(ctx->ev_pool[e_begin], ctx->stream);
-  int rc = upload_traj(ctx, N, coeffs, T, /*clear_nonfinite=*/true);   // (k_prep also clears the non-finite counter)
+  int rc = upload_traj(ctx, N, coeffs, T, TrajUse::evaluation, /*clear_nonfinite=*/true);   // (k_prep also clears the non-finite counter)
   if (rc) return rc;
   if ((rc = build_layer_tables(ctx))) return rc;
   const bool fork = ctx->nbatch > 1;   // one batch: the whole chain stays on the main stream (no cross-stream hand-offs)
@@ -616,9 +536,7 @@ int enqueue_queries(svsdf_ctx *ctx, int N, const double *coeffs, const double *T
     hipStream_t st = batch_stream(ctx, b);
     BatchCtl *ctl = ctx->d_ctl + b;
     if (fork) HIPCHK(hipStreamWaitEvent(st, ctx->ev_prep, 0));
-    QuerySet qm{};
-    qm.qx = ctx->d_px; qm.qy = ctx->d_py; qm.stride = 0; qm.count_ptr = nullptr;
-    qm.count_fixed = ctx->bcount[b]; qm.list = nullptr; qm.base = ctx->bstart[b]; qm.n_outer = 1;
+    const QuerySet qm = main_queries(ctx, b);
     const double cull_thresh = (allow_cull && ctx->cull && ctx->cull_ok) ? ctx->cfg.safety_hor + 1e-9 : std::numeric_limits<double>::infinity();
     launch_solve(ctx, ctx->G, st, qm, ctx->bcount[b], ctx->d_sdf, ctx->d_t, ctl, 0, cull_thresh);
     launch_classify(ctx, st, b);
@@ -640,22 +558,18 @@ int enqueue_queries(svsdf_ctx *ctx, int N, const double *coeffs, const double *T
 // for every resident point, in the sorted shard order -- the main solve without cull, classification and GSIP rounds
 // (svsdf_swept_outline: the zero set only needs the sign and a Lipschitz value next to it).
 int swept_field(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, double *sdf_sorted) {
-  if (ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "host-only context: no device entry points");
-  if (!ctx->points_set) return fail(ctx, SVSDF_ERR_NO_POINTS, "svsdf_set_points has not been called");
+  if (int rc = require_resident(ctx)) return rc;
   if (ctx->P == 0) return SVSDF_OK;
   HIPCHK(hipSetDevice(ctx->device));
   begin_evaluation(ctx);
-  int rc = upload_traj(ctx, N, coeffs, T);
+  int rc = upload_traj(ctx, N, coeffs, T, TrajUse::evaluation);
   if (rc) return rc;
   if ((rc = build_layer_tables(ctx))) return rc;
   if (ctx->nbatch > 1) HIPCHK(hipEventRecord(ctx->ev_prep, ctx->stream));
   for (int b = 0; b < ctx->nbatch; ++b) {
     hipStream_t st = batch_stream(ctx, b);
     if (ctx->nbatch > 1) HIPCHK(hipStreamWaitEvent(st, ctx->ev_prep, 0));
-    QuerySet qm{};
-    qm.qx = ctx->d_px; qm.qy = ctx->d_py; qm.stride = 0; qm.count_ptr = nullptr;
-    qm.count_fixed = ctx->bcount[b]; qm.list = nullptr; qm.base = ctx->bstart[b]; qm.n_outer = 1;
-    launch_solve(ctx, ctx->G, st, qm, ctx->bcount[b], ctx->d_sdf, ctx->d_t, ctx->d_ctl + b, 0);
+    launch_solve(ctx, ctx->G, st, main_queries(ctx, b), ctx->bcount[b], ctx->d_sdf, ctx->d_t, ctx->d_ctl + b, 0);
   }
   rc = join_batches(ctx);
   if (rc) return rc;
@@ -838,22 +752,14 @@ void fill_mode_stats(svsdf_ctx *ctx) {
 
 // Whole device pipeline of ONE device; leaves [cost, gradC, gradT] (19N+1 doubles) in d_out / h_out.
 int run_pipeline_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double *T) {
-  if (ctx->host_only) return fail(ctx, SVSDF_ERR_NO_DEVICE, "host-only context: no device entry points");
-  if (!ctx->points_set) return fail(ctx, SVSDF_ERR_NO_POINTS, "svsdf_set_points has not been called");
+  if (int rc = require_resident(ctx)) return rc;
   if (ctx->P == 0) {
     // an obstacle-free window (or an empty stripe): the reference's loop over parallel_points_num == 0 adds
     // nothing (BEO:785) and the callback returns energy + rho * sum(T).  The trajectory is still validated and
     // traj_duration updated (SWM:376-385); the partial is zero on the host and on the device (collectives).
-    if (N < 1 || N > kMaxPieces) return fail(ctx, SVSDF_ERR_INVALID, "N out of range [1, 128]");
-    double td = 0.0;
-    for (int i = 0; i < N; ++i) {
-      if (!std::isfinite(T[i])) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite duration");
-      if (!(T[i] > 0.0)) return fail(ctx, SVSDF_ERR_INVALID, "piece durations must be positive");
-      td += T[i];
-    }
-    for (size_t i = 0; i < 18 * (size_t)N; ++i)
-      if (!std::isfinite(coeffs[i])) return fail(ctx, SVSDF_ERR_NONFINITE, "non-finite trajectory input");
-    if (td < 3 * 1e2 || !ctx->have_duration) { ctx->traj_duration = td; ctx->have_duration = true; }
+    const svsdf_traj::TrajCheck chk = svsdf_traj::check_traj(N, coeffs, T);
+    if (chk.code) return fail(ctx, chk.code, chk.reason);
+    svsdf_traj::update_duration(chk.td, ctx->traj_duration, ctx->have_duration);
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(hipMemsetAsync(ctx->d_out, 0, kOutDoubles * sizeof(double), ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1237,7 +1143,7 @@ int debug_sdf_at(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, s
   ctx->ev_used = 0;
   const size_t e0 = next_event(ctx);
   (void)hipEventRecord(ctx->ev_pool[e0], ctx->stream);
-  int rc = upload_traj(ctx, N, coeffs, T);
+  int rc = upload_traj(ctx, N, coeffs, T, TrajUse::evaluation);
   if (rc) return rc;
   // (an early return below frees the scratch, and the owner's free waits for the device: no queued copy still reads pxy / t or
   // writes out8 once this function has returned)
@@ -1257,8 +1163,6 @@ int debug_sdf_at(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, s
   HIPCHK_AS("svsdf_debug_sdf_at", hipStreamSynchronize(ctx->stream));
   return SVSDF_OK;
 }
-
-int upload_traj_only(svsdf_ctx *ctx, int N, const double *coeffs, const double *T) { return upload_traj(ctx, N, coeffs, T); }
 
 // mismatch count of the kernels' inlined sincos against the device library's (svsdf_debug_sincos_mismatches)
 long long sincos_mismatches(svsdf_ctx *ctx, double lo, double hi, int n) {
