@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "svsdf_kernels.hpp"
+#include "svsdf_ordkey.hpp"
 
 namespace svsdf {
 
@@ -162,6 +163,121 @@ k_clr_level(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__res
   clr_block_reduce(mine, partials);
 }
 
+// ---- svsdf_point_clearance: the same search with one minimum PER POINT ("per point").  Same intervals, same
+// bound, same evaluations; what differs is where the running minima live and what a pair is settled against.
+//   U[p]     smallest value evaluated so far for point p          S[p]    smallest bound of p's settled pairs
+//   open[p]  smallest bound of p's pairs that split in the level that ran last      tw[p]   witness time of U[p]
+// all as ord_key() keys lowered with the integer atomicMin: the minimum of a set does not depend on the order its members
+// arrive in, so every array is the same from run to run.  A level settles pair (p, j, k) against snap[p], the copy of U[p]
+// taken before the level's first launch (k_pclr_snapshot): the set of pairs a level emits depends neither on lane order nor
+// on how the level was sliced.
+// The witness: a lane that lowers U[p] stores the "none" key to tw[p] (every such store writes the same value); after the
+// launch k_pclr_witness goes over the launch's evaluations and lowers tw[p] to the time of each one whose value equals
+// U[p].  An evaluation of an earlier launch that still equals U[p] was recorded by that launch's pass and is not cleared,
+// since U[p] did not go down after it: tw[p] ends as the smallest time among all evaluations that attain U[p].
+// Kernels: k_pclr_seed, k_pclr_tile_max, k_pclr_broad (seed and broad phase per tile), k_pclr_snapshot,
+// k_pclr_level0<SHAPE>, k_pclr_level<SHAPE>, k_pclr_witness (a level), k_pclr_final (brackets and states).
+enum : unsigned char { kPclrConverged = 0, kPclrFar = 1, kPclrSafe = 2, kPclrUnsafe = 3, kPclrOpen = 4 };   // SVSDF_POINT_*
+struct PclrState { unsigned long long *U, *S, *open, *tw; const unsigned long long *snap; };   // P keys each
+struct PclrEval { double f, t; };                        // one per evaluation of a launch, beside its pair
+struct PclrRule { double eps, cap, target; };            // target NaN: none
+// What the host reads per launch; integer atomics only.
+struct PclrCounters { unsigned long long out_count, evals; unsigned overflow, pad_; };
+
+// Lower a key; true when this call did.  The plain load is a filter only: a stale value is never below the current one.
+__device__ __forceinline__ bool pclr_key_min(unsigned long long *addr, unsigned long long key) {
+  if (key >= __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return false;
+  return atomicMin(addr, key) > key;
+}
+__device__ __forceinline__ void pclr_value(const PclrState &s, unsigned pt, double f) {
+  if (f == f && pclr_key_min(&s.U[pt], ord_key(f))) s.tw[pt] = kOrdKeyPosInf;   // (a NaN never becomes a minimum)
+}
+
+// A pair's verdict against its point's snapshot: settled iff lb >= min(snap - eps, cap), under a target also iff
+// lb >= target or snap < target (the point is decided); any other pair splits into its halves.
+__device__ __forceinline__ void pclr_settle_or_split(double lb, const PclrRule &r, const PclrState &s, unsigned pt, unsigned j,
+                                                     unsigned long long k, ClrPair *__restrict__ out, unsigned out_cap,
+                                                     PclrCounters *__restrict__ cnt) {
+  const double u = ord_unkey(s.snap[pt]);
+  const double a = u - r.eps, thr = a < r.cap ? a : r.cap;
+  const bool settled = lb >= thr || (r.target == r.target && (lb >= r.target || u < r.target));
+  const unsigned long long key = ord_key(lb == lb ? lb : -__builtin_huge_val());
+  if (settled) { pclr_key_min(&s.S[pt], key); return; }
+  pclr_key_min(&s.open[pt], key);
+  const unsigned long long slot = atomicAdd(&cnt->out_count, 2ull);
+  if (slot + 2ull > (unsigned long long)out_cap) { cnt->overflow = 1u; return; }   // (the host sizes the buffer for every pair splitting)
+  ClrPair c;
+  c.pt = pt; c.j = j; c.k = 2ull * k;
+  out[slot] = c;
+  c.k = 2ull * k + 1ull;
+  out[slot + 1] = c;
+}
+// the lanes' evaluation counts: summed over the wave, one integer atomic per wave
+__device__ __forceinline__ void pclr_count_evals(unsigned long long evals, PclrCounters *__restrict__ cnt) {
+  for (int o = 32; o > 0; o >>= 1) evals += __shfl_down(evals, o);
+  if ((threadIdx.x & 63u) == 0u && evals) atomicAdd(&cnt->evals, evals);
+}
+
+// Level 0 and the seed (`emit == 0`: values only): k_clr_level0's wave per (tile, interval), evaluation v * 64 + lane.
+template <int SHAPE>
+__global__ void __launch_bounds__(kClrBlock)
+k_pclr_level0(ShapeParams sp, const double *__restrict__ px_, const double *__restrict__ py_, unsigned P,
+              const Pose *__restrict__ mid, const double *__restrict__ V_, const double *__restrict__ W_, double w, double dur,
+              const ClrTilePair *__restrict__ tp, unsigned ntp, PclrRule rule, int emit, PclrState s, PclrEval *__restrict__ ev,
+              ClrPair *__restrict__ out, unsigned out_cap, PclrCounters *__restrict__ cnt) {
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = kClrBlock / 64;
+  const double h = clr_half_width(w, 0);
+  unsigned long long evals = 0ull;
+  for (unsigned v = blockIdx.x * waves + wave; v < ntp; v += gridDim.x * waves) {
+    const ClrTilePair q = tp[v];
+    const unsigned pt = q.tile * (unsigned)kClrTile + lane;
+    if (pt >= P) continue;
+    const Pose p = mid[q.j];
+    const double px = px_[pt], py = py_[pt];
+    const double f = sdf_from_pose<SHAPE>(sp, p, px, py);
+    PclrEval e;
+    e.f = f; e.t = clr_mid(q.j, 0ull, 0, w, dur);
+    ev[(size_t)v * kClrTile + lane] = e;
+    evals += 1ull;
+    pclr_value(s, pt, f);
+    if (!emit) continue;
+    const double dx = px - p.x, dy = py - p.y;
+    const double lb = clr_lower(f, h, V_[q.j], W_[q.j], sqrt(dx * dx + dy * dy));
+    pclr_settle_or_split(lb, rule, s, pt, q.j, 0ull, out, out_cap, cnt);
+  }
+  pclr_count_evals(evals, cnt);
+}
+
+// Level L >= 1: k_clr_level's lane per pair, evaluation i beside pair i.
+template <int SHAPE>
+__global__ void __launch_bounds__(kClrBlock)
+k_pclr_level(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__restrict__ px_, const double *__restrict__ py_,
+             const double *__restrict__ V_, const double *__restrict__ W_, double w, int L, const ClrPair *__restrict__ in,
+             unsigned n, PclrRule rule, PclrState s, PclrEval *__restrict__ ev, ClrPair *__restrict__ out, unsigned out_cap,
+             PclrCounters *__restrict__ cnt) {
+  extern __shared__ double clr_lds[];
+  const TrajL tr = stage_traj(trg, clr_lds);
+  const double h = clr_half_width(w, L);
+  PieceCache pc = piece_cache_init();
+  unsigned long long evals = 0ull;
+  for (unsigned i = blockIdx.x * kClrBlock + threadIdx.x; i < n; i += gridDim.x * kClrBlock) {
+    const ClrPair q = in[i];
+    const double t = clr_mid(q.j, q.k, L, w, tr.dur);
+    const Pose p = pose_at(tr, t, pc);
+    const double px = px_[q.pt], py = py_[q.pt];
+    const double f = sdf_from_pose<SHAPE>(sp, p, px, py);
+    PclrEval e;
+    e.f = f; e.t = t;
+    ev[i] = e;
+    evals += 1ull;
+    pclr_value(s, q.pt, f);
+    const double dx = px - p.x, dy = py - p.y;
+    const double lb = clr_lower(f, h, V_[q.j], W_[q.j], sqrt(dx * dx + dy * dy));
+    pclr_settle_or_split(lb, rule, s, q.pt, q.j, q.k, out, out_cap, cnt);
+  }
+  pclr_count_evals(evals, cnt);
+}
+
 #ifdef SVSDF_CLR_TU   // shape-independent kernels: compiled once, by svsdf_clearance.hip
 
 // Bounding circle of points [64 i, 64 i + 64) of the cloud: centre of their box, radius the largest distance to it, rounded up.
@@ -246,6 +362,114 @@ k_clr_reduce(const ClrPartial *__restrict__ partials, unsigned n, ClrRecord *__r
   clr_block_reduce(mine, s_one);   // (blockIdx.x == 0: lands in s_one[0])
   __syncthreads();
   if (threadIdx.x == 0) { rec->best = s_one[0].best; rec->settled_min = s_one[0].settled_min; rec->open_min = s_one[0].open_min; rec->evals = s_one[0].evals; }
+}
+
+// ---- svsdf_point_clearance, shape-independent kernels
+
+__global__ void __launch_bounds__(kClrBlock)
+k_pclr_fill(unsigned long long *__restrict__ a, size_t n, unsigned long long value) {
+  for (size_t i = (size_t)blockIdx.x * kClrBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kClrBlock) a[i] = value;
+}
+
+// Before a level's first launch: the thresholds' snapshot of U, and no open bound yet.
+__global__ void __launch_bounds__(kClrBlock)
+k_pclr_snapshot(const unsigned long long *__restrict__ U, unsigned long long *__restrict__ snap, unsigned long long *__restrict__ open,
+                unsigned P) {
+  for (unsigned p = blockIdx.x * kClrBlock + threadIdx.x; p < P; p += gridDim.x * kClrBlock) { snap[p] = U[p]; open[p] = kOrdKeyPosInf; }
+}
+
+// The seed: per tile the interval with the smallest cheap bound (ties: the smallest j) -- k_clr_broad's minimum, taken per
+// tile.  One wave per tile.
+__global__ void __launch_bounds__(kClrBlock)
+k_pclr_seed(const ClrTileCircle *__restrict__ tiles, unsigned ntiles, const Pose *__restrict__ mid, const double *__restrict__ V_,
+            unsigned n0, double w, double r_bound, ClrTilePair *__restrict__ seed) {
+  const unsigned lane = threadIdx.x & 63u, tile = blockIdx.x * (kClrBlock / 64) + (threadIdx.x >> 6);
+  if (tile >= ntiles) return;   // (the whole wave)
+  const double h = clr_half_width(w, 0);
+  const ClrTileCircle c = tiles[tile];
+  double best = __builtin_huge_val();
+  unsigned bj = 0xffffffffu;
+  for (unsigned j = lane; j < n0; j += 64u) {
+    const double cheap = clr_cheap(c, mid[j], h, V_[j], r_bound);
+    if (cheap < best || bj == 0xffffffffu) { best = cheap == cheap ? cheap : __builtin_huge_val(); bj = j; }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ob = __shfl_xor(best, o);
+    const unsigned oj = __shfl_xor(bj, o);
+    if (ob < best || (ob == best && oj < bj)) { best = ob; bj = oj; }
+  }
+  if (lane == 0u) { ClrTilePair q; q.tile = tile; q.j = bj; seed[tile] = q; }   // (n0 >= 1: lane 0 always holds an interval)
+}
+
+// After the seed: the largest U of every tile, and no dropped bound yet.
+__global__ void __launch_bounds__(kClrBlock)
+k_pclr_tile_max(const unsigned long long *__restrict__ U, unsigned P, unsigned ntiles, double *__restrict__ tmax,
+                unsigned long long *__restrict__ tdrop) {
+  const unsigned i = blockIdx.x * kClrBlock + threadIdx.x;
+  if (i >= ntiles) return;
+  const unsigned p0 = i * (unsigned)kClrTile, p1 = (p0 + (unsigned)kClrTile < P) ? p0 + (unsigned)kClrTile : P;
+  unsigned long long m = U[p0];
+  for (unsigned p = p0 + 1; p < p1; ++p) m = U[p] > m ? U[p] : m;
+  tmax[i] = ord_unkey(m);
+  tdrop[i] = kOrdKeyPosInf;
+}
+
+// The broad phase per tile: (tile, interval) is kept iff its cheap bound is <= min(cap, the tile's largest U).  A dropped
+// pair's bound lies above every U[p] of its tile, or above cap: it cannot lower a U[p] (every value of the pair is above
+// the bound), and it lowers lower[p] only below a cap -- through tdrop, the smallest dropped bound of the tile, which
+// k_pclr_final takes into every lower[p] of the tile (without a cap it is above U[p] and changes nothing).
+// list == null: count, and record the dropped bounds; list != null: fill (cap_entries entries).
+__global__ void __launch_bounds__(kClrBlock)
+k_pclr_broad(const ClrTileCircle *__restrict__ tiles, unsigned ntiles, const Pose *__restrict__ mid, const double *__restrict__ V_,
+             unsigned n0, double w, double r_bound, double cap, const double *__restrict__ tmax, ClrTilePair *__restrict__ list,
+             unsigned long long cap_entries, unsigned long long *__restrict__ count, unsigned long long *__restrict__ tdrop) {
+  const double h = clr_half_width(w, 0);
+  const unsigned long long total = (unsigned long long)ntiles * n0;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * kClrBlock + threadIdx.x; i < total; i += (unsigned long long)gridDim.x * kClrBlock) {
+    const unsigned tile = (unsigned)(i / n0), j = (unsigned)(i % n0);
+    const double cheap = clr_cheap(tiles[tile], mid[j], h, V_[j], r_bound);
+    const double tm = tmax[tile], thr = cap < tm ? cap : tm;
+    if (!(cheap > thr)) {
+      const unsigned long long slot = atomicAdd(count, 1ull);
+      if (list && slot < cap_entries) { ClrTilePair q; q.tile = tile; q.j = j; list[slot] = q; }
+    } else if (!list) {
+      pclr_key_min(&tdrop[tile], ord_key(cheap));
+    }
+  }
+}
+
+// After a launch: the witness time of every evaluation that attains its point's U.  tp != null: level 0 (evaluation
+// v * 64 + lane of tile pair v), else pair i of `in`.
+__global__ void __launch_bounds__(kClrBlock)
+k_pclr_witness(const ClrTilePair *__restrict__ tp, const ClrPair *__restrict__ in, unsigned n, unsigned P,
+               const PclrEval *__restrict__ ev, const unsigned long long *__restrict__ U, unsigned long long *__restrict__ tw) {
+  for (unsigned i = blockIdx.x * kClrBlock + threadIdx.x; i < n; i += gridDim.x * kClrBlock) {
+    const unsigned pt = tp ? tp[i >> 6].tile * (unsigned)kClrTile + (i & 63u) : in[i].pt;
+    if (pt >= P) continue;
+    const PclrEval e = ev[i];
+    if (e.f == e.f && ord_key(e.f) == U[pt]) pclr_key_min(&tw[pt], ord_key(e.t));
+  }
+}
+
+// The end of the search, in shard order: lower[p] = min(U, S, open, the tile's dropped bound), and the state.
+__global__ void __launch_bounds__(kClrBlock)
+k_pclr_final(unsigned P, PclrState s, const unsigned long long *__restrict__ tdrop, PclrRule r, double *__restrict__ lower,
+             double *__restrict__ upper, double *__restrict__ tw, unsigned char *__restrict__ state) {
+  for (unsigned p = blockIdx.x * kClrBlock + threadIdx.x; p < P; p += gridDim.x * kClrBlock) {
+    const double u = ord_unkey(s.U[p]);
+    unsigned long long k = s.U[p];
+    k = s.S[p] < k ? s.S[p] : k;
+    k = s.open[p] < k ? s.open[p] : k;
+    k = tdrop[p / (unsigned)kClrTile] < k ? tdrop[p / (unsigned)kClrTile] : k;
+    const double lo = ord_unkey(k);
+    const bool has_target = r.target == r.target;
+    unsigned char st = kPclrOpen;
+    if (has_target && u < r.target) st = kPclrUnsafe;
+    else if (has_target && lo >= r.target) st = kPclrSafe;
+    else if (lo >= r.cap) st = kPclrFar;
+    else if (u - lo <= r.eps) st = kPclrConverged;
+    lower[p] = lo; upper[p] = u; tw[p] = ord_unkey(s.tw[p]); state[p] = st;
+  }
 }
 
 #endif  // SVSDF_CLR_TU

@@ -483,6 +483,8 @@ int upload_traj(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, Tr
 // ---- svsdf_clearance.hip
 int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, const svsdf_clearance_params &prm,
                        svsdf_clearance_result *out);
+int point_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, const svsdf_point_clearance_params &prm,
+                         double *lower, double *upper, double *t_witness, unsigned char *state, svsdf_point_clearance_result *out);
 // ---- svsdf_group.hip
 int upload_group_device(svsdf_ctx *ctx, const double *d_xyz, size_t P);
 int group_run(svsdf_ctx *ctx, const std::function<int(int)> &f);

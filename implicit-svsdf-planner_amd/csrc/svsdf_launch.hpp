@@ -42,6 +42,11 @@ struct ClrLaunch {     // arguments of k_clr_level0<SHAPE> (L == 0: tp / ntp, mi
   const double *V, *W; double w, dur; int L; const ClrTilePair *tp; const ClrPair *in; unsigned n; double thr; int emit;
   ClrPair *out; unsigned out_cap; ClrRecord *rec; ClrPartial *partials;
 };
+struct PclrLaunch {    // arguments of k_pclr_level0<SHAPE> (L == 0: tp / ntp, mid, emit) and k_pclr_level<SHAPE> (L >= 1: traj, in / n)
+  const TrajDev *traj; ShapeParams sp; const double *px, *py; unsigned P; const Pose *mid; const double *V, *W; double w, dur;
+  int L; const ClrTilePair *tp; const ClrPair *in; unsigned n; PclrRule rule; int emit; PclrState s; PclrEval *ev;
+  ClrPair *out; unsigned out_cap; PclrCounters *cnt;
+};
 // lane-group widths the scaled solve is instantiated for (§4c: a reduced plan space); scaled_lanes maps any width onto them
 constexpr int kScaledLanes[3] = {4, 8, 32};
 inline int scaled_lanes(int G) { return G >= 32 ? 32 : G >= 8 ? 8 : 4; }
@@ -66,6 +71,7 @@ bool launch_k_succ(int shape, unsigned grid, hipStream_t st, ShapeParams sp, con
                    const double *parent_yaw, double *yaw_out, unsigned char *stage_out);
 bool launch_k_astar(int shape, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const AstarDev &a, int slice);
 bool launch_k_clr(int shape, unsigned grid, size_t lds, hipStream_t st, const ClrLaunch &a);
+bool launch_k_pclr(int shape, unsigned grid, size_t lds, hipStream_t st, const PclrLaunch &a);
 // shape-independent front-end kernels (svsdf_pipeline.hip)
 void launch_k_pack_kernel_rows(hipStream_t st, const unsigned char *map, int ks, int count, unsigned long long *rows);
 void launch_k_yaw_free(hipStream_t st, const unsigned long long *occ, int row_words, const unsigned long long *krows, int ks,
@@ -87,7 +93,8 @@ void launch_k_yaw_free(hipStream_t st, const unsigned long long *occ, int row_wo
   bool launch_k_succ_s##K(int shape, unsigned grid, hipStream_t st, ShapeParams sp, const FrontMapDev &fm,                      \
                           const int *parent_ij, const double *parent_yaw, double *yaw_out, unsigned char *stage_out);       \
   bool launch_k_astar_s##K(int shape, hipStream_t st, ShapeParams sp, const FrontMapDev &fm, const AstarDev &a, int slice);       \
-  bool launch_k_clr_s##K(int shape, unsigned grid, size_t lds, hipStream_t st, const ClrLaunch &a);
+  bool launch_k_clr_s##K(int shape, unsigned grid, size_t lds, hipStream_t st, const ClrLaunch &a);                            \
+  bool launch_k_pclr_s##K(int shape, unsigned grid, size_t lds, hipStream_t st, const PclrLaunch &a);
 SVSDF_DECLARE_SLICE(0)
 SVSDF_DECLARE_SLICE(1)
 SVSDF_DECLARE_SLICE(2)

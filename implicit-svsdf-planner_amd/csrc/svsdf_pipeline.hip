@@ -173,6 +173,10 @@ bool launch_k_clr(int shape, unsigned grid, size_t lds, hipStream_t st, const Cl
   shape = svsdf_impl::compiled_shape(shape);
   SVSDF_SLICE_DISPATCH(launch_k_clr, grid, lds, st, a)
 }
+bool launch_k_pclr(int shape, unsigned grid, size_t lds, hipStream_t st, const PclrLaunch &a) {
+  shape = svsdf_impl::compiled_shape(shape);
+  SVSDF_SLICE_DISPATCH(launch_k_pclr, grid, lds, st, a)
+}
 void launch_k_pack_kernel_rows(hipStream_t st, const unsigned char *map, int ks, int count, unsigned long long *rows) {
   hipLaunchKernelGGL(k_pack_kernel_rows, dim3((unsigned)((ks * count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, map, ks,
                      count, rows);

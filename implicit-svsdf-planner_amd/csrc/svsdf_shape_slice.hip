@@ -1,7 +1,7 @@
 // svsdf_shape_slice.hip -- one slice of the shape-templated kernels (compile with -DSVSDF_SLICE=k, k = 0 .. 3).
 //
 // Slice k instantiates k_solve / k_round / k_tail / k_classify / k_rbound / k_subsw / k_shape_kernels / k_succ /
-// k_astar / k_debug_sdf_at / k_clr_level0 / k_clr_level for the shapes with id % 4 == k and exports the launchers svsdf_pipeline.hip dispatches to
+// k_astar / k_debug_sdf_at / k_clr_level0 / k_clr_level / k_pclr_level0 / k_pclr_level for the shapes with id % 4 == k and exports the launchers svsdf_pipeline.hip dispatches to
 // (svsdf_launch.hpp).  k_solve, k_classify and k_debug_sdf_at are each one template with a rigid and a scaled instantiation
 // (an empty parameter pack or ScaleDev, svsdf_kernels.hpp ScaleArg); with_scale picks between them at the one place each is
 // launched.  Splitting the ~580 kernel instantiations over four translation units lets the build run in parallel (one TU
@@ -200,6 +200,22 @@ bool clr_s(unsigned grid, size_t lds, hipStream_t st, const ClrLaunch &a) {
   }
 }
 
+// svsdf_point_clearance (svsdf_clearance.hpp): the same two kernels with per-point minima
+template <int S>
+bool pclr_s(unsigned grid, size_t lds, hipStream_t st, const PclrLaunch &a) {
+  if constexpr (!shape_enabled<S>()) {
+    return false;
+  } else {
+    if (a.L == 0)
+      hipLaunchKernelGGL((k_pclr_level0<S>), dim3(grid), dim3(kClrBlock), 0, st, a.sp, a.px, a.py, a.P, a.mid, a.V, a.W, a.w, a.dur,
+                         a.tp, a.n, a.rule, a.emit, a.s, a.ev, a.out, a.out_cap, a.cnt);
+    else
+      hipLaunchKernelGGL((k_pclr_level<S>), dim3(grid), dim3(kClrBlock), lds, st, a.traj, a.sp, a.px, a.py, a.V, a.W, a.w, a.L, a.in,
+                         a.n, a.rule, a.s, a.ev, a.out, a.out_cap, a.cnt);
+    return true;
+  }
+}
+
 }  // namespace
 
 #define SLICE_SWITCH(CALL)                                        \
@@ -268,6 +284,11 @@ bool SLICE_FN(launch_k_astar)(int shape, hipStream_t st, ShapeParams sp, const F
 }
 bool SLICE_FN(launch_k_clr)(int shape, unsigned grid, size_t lds, hipStream_t st, const ClrLaunch &a) {
 #define CALL(S) clr_s<S>(grid, lds, st, a)
+  SLICE_SWITCH(CALL)
+#undef CALL
+}
+bool SLICE_FN(launch_k_pclr)(int shape, unsigned grid, size_t lds, hipStream_t st, const PclrLaunch &a) {
+#define CALL(S) pclr_s<S>(grid, lds, st, a)
   SLICE_SWITCH(CALL)
 #undef CALL
 }

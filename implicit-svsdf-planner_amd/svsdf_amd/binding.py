@@ -37,6 +37,7 @@ EXPORTS = [
     "svsdf_map_build_device", "svsdf_map_device_get_info", "svsdf_map_device_cells", "svsdf_frontend_set_map_device",
     "svsdf_set_points_from_map", "svsdf_map_device_points", "svsdf_path_waypoints",
     "svsdf_clearance_params_default", "svsdf_min_clearance", "svsdf_motion_bounds",
+    "svsdf_point_clearance_params_default", "svsdf_point_clearance",
 ]
 
 
@@ -147,6 +148,23 @@ class ClearanceResult(C.Structure):
 
 
 CLEARANCE_STATUS = ["CONVERGED", "SAFE", "UNSAFE", "BUDGET"]     # SVSDF_CLEARANCE_*
+
+
+class PointClearanceParams(C.Structure):
+    """svsdf_point_clearance_params (include/svsdf_c.h)."""
+    _fields_ = [("struct_size", C.c_size_t), ("eps", C.c_double), ("cap", C.c_double), ("target", C.c_double),
+                ("max_evals", C.c_ulonglong), ("pair_capacity", C.c_size_t)]
+
+
+class PointClearanceResult(C.Structure):
+    """svsdf_point_clearance_result (include/svsdf_c.h)."""
+    _fields_ = [("status", C.c_int), ("levels", C.c_int), ("counts", C.c_ulonglong * 5), ("lower", C.c_double),
+                ("upper", C.c_double), ("t_witness", C.c_double), ("point_index", C.c_longlong), ("evals", C.c_ulonglong),
+                ("pairs", C.c_ulonglong), ("tile_pairs", C.c_ulonglong), ("tile_pairs_kept", C.c_ulonglong),
+                ("device_ms", C.c_double)]
+
+
+POINT_STATE = ["CONVERGED", "FAR", "SAFE", "UNSAFE", "OPEN"]     # SVSDF_POINT_*
 
 
 class OutlineStats(C.Structure):
@@ -265,6 +283,10 @@ def lib():
     L.svsdf_clearance_params_default.restype = None
     L.svsdf_min_clearance.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(ClearanceParams), C.POINTER(ClearanceResult)]
     L.svsdf_motion_bounds.argtypes = [C.c_int, _dp, _dp, C.c_double, C.c_double, _dp]
+    L.svsdf_point_clearance_params_default.argtypes = [C.POINTER(PointClearanceParams)]
+    L.svsdf_point_clearance_params_default.restype = None
+    L.svsdf_point_clearance.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(PointClearanceParams), _dp, _dp, _dp,
+                                        C.POINTER(C.c_ubyte), C.POINTER(PointClearanceResult)]
     if hasattr(L, "svsdf_mesh_section"):   # (the guards: absent only from A/B libraries built from older commits, tools/build_ref_variant.sh)
         L.svsdf_mesh_section.argtypes = [_dp, C.c_size_t, _ip, C.c_size_t, C.c_double, _dp, C.c_size_t, C.POINTER(C.c_size_t), _ip,
                                          C.c_size_t, C.POINTER(C.c_size_t)]
@@ -616,6 +638,7 @@ class SvsdfContext:
             raise SvsdfError("svsdf_create failed: " + self.L.svsdf_last_error_string(None).decode())
         self.ctx = C.c_void_p(h)
         self.head_state, self.tail_state = hs, ts
+        self._world_size = int(world_size)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -964,6 +987,37 @@ class SvsdfContext:
         out["status"] = CLEARANCE_STATUS[res.status]
         out["point_xy"] = (res.point_xy[0], res.point_xy[1])
         return out
+
+    def point_clearance(self, coeffs, T, eps=1e-3, cap=None, target=None, max_evals=0, pair_capacity=0, struct_size=None):
+        """Certified bracket lower[p] <= c_p <= upper[p] on every resident point's minimum over [0, sum T] of the
+        SDF-at-time, with the time of the evaluation that gave upper[p] (svsdf_point_clearance).  Returns (lower, upper,
+        t_witness, state names, result): four arrays in the svsdf_set_points order (the states as POINT_STATE names) and
+        the fields of svsdf_point_clearance_result as a dict (status as one of CLEARANCE_STATUS, counts keyed by state
+        name).  cap=None: no cap; target=None: no target."""
+        T = _f64(T)
+        cm = _colmajor(coeffs)
+        prm = PointClearanceParams()
+        self.L.svsdf_point_clearance_params_default(C.byref(prm))
+        prm.eps = float(eps)
+        if cap is not None:
+            prm.cap = float(cap)
+        if target is not None:
+            prm.target = float(target)
+        prm.max_evals, prm.pair_capacity = int(max_evals), int(pair_capacity)
+        if struct_size is not None:
+            prm.struct_size = int(struct_size)
+        P = int(self.num_points())
+        if P and self._world_size > 1:      # a rank's shard: the arrays span the whole svsdf_set_points array
+            P = int(self.shard_indices().max()) + 1
+        lower, upper, tw = np.zeros(P), np.zeros(P), np.zeros(P)
+        state = np.zeros(P, dtype=np.uint8)
+        res = PointClearanceResult()
+        self._chk(self.L.svsdf_point_clearance(self.ctx, len(T), _p(cm), _p(T), C.byref(prm), _p(lower), _p(upper), _p(tw),
+                                               state.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(res)), "svsdf_point_clearance")
+        out = {k: getattr(res, k) for k, _ in PointClearanceResult._fields_}
+        out["status"] = CLEARANCE_STATUS[res.status]
+        out["counts"] = {name: int(res.counts[i]) for i, name in enumerate(POINT_STATE)}
+        return lower, upper, tw, np.array(POINT_STATE)[state], out
 
     def sincos_mismatches(self, lo, hi, n):
         return int(self.L.svsdf_debug_sincos_mismatches(self.ctx, float(lo), float(hi), int(n)))

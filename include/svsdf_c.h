@@ -572,6 +572,50 @@ typedef struct svsdf_clearance_result {
 void svsdf_clearance_params_default(svsdf_clearance_params *p);
 int svsdf_min_clearance(svsdf_ctx *ctx, int N, const double *coeffs, const double *T,
                         const svsdf_clearance_params *params /* may be NULL */, svsdf_clearance_result *out);
+/* The same question per point: for every point p of the svsdf_set_points array, in that array's order, a certified bracket
+ *   lower[p] <= c_p <= upper[p],   c_p = min over t in [0, sum T] of getSDFAtTimeStamp<false>(p, t)      (SWM:741-750)
+ * -- for an exterior point the swept-volume distance itself, for a colliding one how deep the collision is -- with
+ * t_witness[p] the time of the evaluation the device made that gave upper[p] (svsdf_debug_sdf_at reproduces it bit for bit;
+ * among all evaluations of p that attain upper[p], the one with the smallest t).  The search is svsdf_min_clearance's
+ * (same intervals, same bound, same evaluations) with one running minimum per point instead of one: per-point values
+ * U_p and settled bounds S_p live on the device as order-preserving integer keys of the doubles, lowered with integer
+ * atomic minima (a minimum does not depend on arrival order: results are bit-reproducible), and a level settles a pair of
+ * point p with bound lb iff lb >= min(U_p - eps, cap) -- under a target also iff lb >= target or U_p < target -- against
+ * the U_p of before the level's first launch.  First every tile of 64 points is evaluated against the interval with its
+ * smallest cheap bound (these count in evals); a (tile, interval) is kept iff its cheap bound is at most
+ * min(cap, the tile's largest U_p).  state[p]:
+ *   CONVERGED  upper - lower <= eps                    FAR     lower >= cap: not refined further
+ *   SAFE       lower >= target                         UNSAFE  upper < target
+ *   OPEN       max_evals or level 44 ended the search first; the bracket is valid all the same
+ * (decided in the order UNSAFE, SAFE, FAR, CONVERGED).  lower, upper, t_witness, state: as many entries as the
+ * svsdf_set_points array each, any may be NULL (a context with world_size > 1 writes the entries of its own shard only).
+ * Results do not depend on pair_capacity; two calls return identical arrays and structs except device_ms.  Context state,
+ * refusals (with this entry's name) and the empty cloud (counts of zero, lower = upper = +infinity, point_index = -1) are
+ * svsdf_min_clearance's; in addition a NaN cap is SVSDF_ERR_INVALID.  A multi-device context searches every stripe on its
+ * own device and scatters the stripes' points; its per-point brackets are valid but need not equal a single-device
+ * context's bit for bit (the seed interval depends on the tile). */
+typedef struct svsdf_point_clearance_params {
+  size_t struct_size;            /* sizeof(svsdf_point_clearance_params) */
+  double eps;                    /* > 0, finite (default 1e-3) */
+  double cap;                    /* +infinity (default): none.  Clearance above cap is not refined */
+  double target;                 /* NaN (default): none.  A point is finished once upper < target or lower >= target */
+  unsigned long long max_evals;  /* as for svsdf_min_clearance; 0: 4 * P * ceil(sum T / 0.15).  The seed and level 0 always run */
+  size_t pair_capacity;          /* as for svsdf_min_clearance */
+} svsdf_point_clearance_params;
+enum { SVSDF_POINT_CONVERGED = 0, SVSDF_POINT_FAR = 1, SVSDF_POINT_SAFE = 2, SVSDF_POINT_UNSAFE = 3, SVSDF_POINT_OPEN = 4,
+       SVSDF_POINT_STATES = 5 };
+typedef struct svsdf_point_clearance_result {
+  int status, levels;            /* SVSDF_CLEARANCE_CONVERGED when no point is OPEN, else SVSDF_CLEARANCE_BUDGET */
+  unsigned long long counts[SVSDF_POINT_STATES];   /* points in each state, indexed by SVSDF_POINT_* */
+  double lower, upper;           /* the minimum over the points of lower[p], of upper[p] */
+  double t_witness; long long point_index;         /* of that upper (ties: the smaller original index); -1: empty cloud */
+  unsigned long long evals, pairs, tile_pairs, tile_pairs_kept;  /* as in svsdf_clearance_result; evals includes the seed's */
+  double device_ms;              /* HIP-event time from the trajectory upload to the states */
+} svsdf_point_clearance_result;
+void svsdf_point_clearance_params_default(svsdf_point_clearance_params *p);
+int svsdf_point_clearance(svsdf_ctx *ctx, int N, const double *coeffs, const double *T,
+                          const svsdf_point_clearance_params *params /* may be NULL */, double *lower, double *upper,
+                          double *t_witness, unsigned char *state, svsdf_point_clearance_result *out);
 /* Host only, no context: rigorous bounds out2 = {max planar speed, max |yaw rate|} of the trajectory on
  * [ta, tb] intersected with [0, sum T] (coeffs, T as for svsdf_eval_penalty).  Per piece, the quartic velocity
  * polynomials restricted to the interval lie in the convex hull of their Bernstein coefficients (the bound of the exact

@@ -8,7 +8,13 @@ At eps 1e-3, without a target and with target = 0: median wall ms of --steps cal
 itself), the device time the call reports, evals, tile_pairs_kept / tile_pairs, levels, pairs; next to them the median
 time of svsdf_query_points on the same cloud and the minimum it reports.  One JSON line per case; nothing is asserted.
 
-    python tools/clearance_timing.py [--steps 5] [--warmup 1] [--cases star sdHorseshoe sdHeart C3] [--out FILE]
+--per-point: svsdf_point_clearance on the same four cases instead, with cap = the context's safety_hor and without a cap
+(median wall ms, device ms, status, levels, evals, pairs, the state counts, the global bracket), and beside them
+svsdf_min_clearance without a target and svsdf_query_points on the same cloud: the ratio to svsdf_min_clearance is the
+figure of interest, and how many of the points svsdf_query_points reads clear (sdf > 0) the certified upper puts in
+collision (upper < 0).
+
+    python tools/clearance_timing.py [--steps 5] [--warmup 1] [--cases star sdHorseshoe sdHeart C3] [--per-point] [--out FILE]
 """
 import argparse
 import json
@@ -33,14 +39,14 @@ ASSETS = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_assets.
 
 
 def _case(name):
-    """(context, coeffs, T, number of points)"""
+    """(context, coeffs, T, number of points, safety_hor)"""
     if name == "C3":
         w = workload.make("C3", minco=svsdf_amd.minco_coeffs)
         kw = dict(safety_hor=w["safety_hor"], weight_p=w["weight_p"], rho=w["rho"], poly_params=w["poly_params"],
                   head_state=w["head_state"], tail_state=w["tail_state"], polygon=w["polygon"])
         ctx = svsdf_amd.SvsdfContext(shape=w["shape"], device=0, **kw)
         ctx.set_points(w["points"])
-        return ctx, w["coeffs"], w["T"], len(w["points"])
+        return ctx, w["coeffs"], w["T"], len(w["points"]), float(w["safety_hor"])
     w = workload.reference_case(name, N=24, iterates=1)
     sc = ASSETS["scenarios"][name]
     c = np.array(ASSETS["maps"][name], dtype=np.float32).astype(np.float64)      # every occupied voxel's centre
@@ -51,7 +57,7 @@ def _case(name):
     ctx = svsdf_amd.SvsdfContext(shape=name, device=0, **kw)
     coeffs, T = ctx.lmbm_prepare(w["xs"][0])
     ctx.set_points(pts)
-    return ctx, coeffs, T, len(pts)
+    return ctx, coeffs, T, len(pts), float(w["safety_hor"])
 
 
 def _median_ms(fn, steps, warmup):
@@ -70,11 +76,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--cases", nargs="+", default=["star", "sdHorseshoe", "sdHeart", "C3"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--per-point", action="store_true", help="time svsdf_point_clearance (see above)")
     a = ap.parse_args()
     for name in a.cases:
-        ctx, coeffs, T, P = _case(name)
+        ctx, coeffs, T, P, safety_hor = _case(name)
         row = {"case": name, "points": P, "pieces": len(T), "duration_s": float(np.sum(T)), "eps": 1e-3}
-        for label, target in (("no_target", None), ("target_0", 0.0)):
+        upper = None
+        if a.per_point:
+            row["mode"] = "per_point"
+            row["safety_hor"] = safety_hor
+            for label, cap in (("cap_safety_hor", safety_hor), ("no_cap", None)):
+                ms, out = _median_ms(lambda: ctx.point_clearance(coeffs, T, eps=1e-3, cap=cap), a.steps, a.warmup)
+                r = out[4]
+                row[label] = {"median_ms": ms, **{k: r[k] for k in ("device_ms", "status", "levels", "lower", "upper", "t_witness",
+                                                                     "point_index", "evals", "pairs", "tile_pairs",
+                                                                     "tile_pairs_kept", "counts")}}
+                upper = out[1]
+        for label, target in (("no_target", None),) if a.per_point else (("no_target", None), ("target_0", 0.0)):
             ms, r = _median_ms(lambda: ctx.min_clearance(coeffs, T, eps=1e-3, target=target), a.steps, a.warmup)
             row[label] = {"median_ms": ms, **{k: r[k] for k in ("device_ms", "status", "levels", "lower", "upper", "t_witness",
                                                                  "evals", "pairs", "tile_pairs", "tile_pairs_kept")}}
@@ -84,6 +102,11 @@ def main():
         ms, rc = _median_ms(lambda: ctx.L.svsdf_query_points(ctx.ctx, len(Tc), _p(cm), _p(Tc), _p(sdf), None, None),
                             a.steps, max(a.warmup, 6))   # (its launch plan settles first)
         row["query_points"] = {"median_ms": ms, "rc": rc, "min_sdf": float(sdf.min()), "sdf_evals": int(ctx.stats()["sdf_evals"])}
+        if upper is not None:   # (sdf is in shard order: bring the certified upper into it)
+            up = upper[ctx.shard_indices()]
+            row["query_points"]["reads_clear"] = int((sdf > 0.0).sum())
+            row["query_points"]["reads_clear_but_upper_below_0"] = int(((sdf > 0.0) & (up < 0.0)).sum())
+            row["per_point_over_min_clearance"] = row["no_cap"]["median_ms"] / row["no_target"]["median_ms"]
         ctx.close()
         line = json.dumps(row)
         print(line, flush=True)
