@@ -1,9 +1,10 @@
-// svsdf_clearance.hip -- svsdf_min_clearance, svsdf_point_clearance and svsdf_motion_bounds (include/svsdf_c.h):
+// svsdf_clearance.hip -- svsdf_min_clearance, svsdf_point_clearance, svsdf_motion_bounds and svsdf_scale_bounds (include/svsdf_c.h):
 // the host side of the certified minimum-clearance search and of its per-point form, and the shape-independent kernels of
 // svsdf_clearance.hpp (SVSDF_CLR_TU).  The shape-templated level kernels live in svsdf_shape_slice.hip behind launch_k_clr /
 // launch_k_pclr.
 #define SVSDF_CLR_TU
 #include "svsdf_ctx.hpp"
+#include "svsdf_scale_host.hpp"
 
 using namespace svsdf;
 
@@ -21,6 +22,35 @@ struct Frontier {   // one chunk of a level's frontier: 2 * cap pairs
 };
 
 constexpr double kInf = std::numeric_limits<double>::infinity();
+
+// The per-interval arrays of a search, one after the other in one buffer: V_j, W_j (svsdf_motion_bounds), then under a scale
+// schedule Imax_j, Q_j, Smin_j, Smax_j (svsdf_scale_bounds), each over level-0 interval j widened by 1e-4 s (as the cull
+// widens 0.075 to 0.0751) and inherited by every descendant.
+std::vector<double> interval_bounds(const svsdf_ctx *ctx, int N, const double *coeffs, const std::vector<double> &S, size_t n0,
+                                    double w) {
+  const double td = S[N];
+  std::vector<double> B((ctx->scaled ? 6 : 2) * n0);
+  svsdf_scale sc{};
+  sc.struct_size = (int)sizeof(svsdf_scale);
+  sc.enabled = 1;
+  sc.c[0] = ctx->scale.cx; sc.amp[0] = ctx->scale.ax; sc.omega[0] = ctx->scale.wx; sc.phase[0] = ctx->scale.phx;
+  sc.c[1] = ctx->scale.cy; sc.amp[1] = ctx->scale.ay; sc.omega[1] = ctx->scale.wy; sc.phase[1] = ctx->scale.phy;
+  for (size_t j = 0; j < n0; ++j) {
+    const double m = clr_mid((unsigned)j, 0ull, 0, w, td), h = clr_half_width(w, 0);
+    double b2[2];
+    svsdf_traj::motion_bounds(N, coeffs, S.data(), m - h - 1e-4, m + h + 1e-4, b2);
+    B[j] = b2[0];
+    B[n0 + j] = b2[1];
+    if (!ctx->scaled) continue;
+    double b4[4];
+    svsdf_traj::scale_bounds(&sc, m - h - 1e-4, m + h + 1e-4, b4);
+    B[2 * n0 + j] = b4[2];   // Imax
+    B[3 * n0 + j] = b4[3];   // Q
+    B[4 * n0 + j] = b4[0];   // Smin
+    B[5 * n0 + j] = b4[1];   // Smax
+  }
+  return B;
+}
 
 }  // namespace
 
@@ -56,15 +86,8 @@ int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double
   if (cap > ((size_t)1 << 30)) return fail(ctx, SVSDF_ERR_INVALID, std::string(who) + ": pair_capacity above 2^30");
   const unsigned long long budget = prm.max_evals ? prm.max_evals : 4ull * P * (unsigned long long)std::ceil(td / 0.15);
 
-  // level-0 motion bounds: the interval widened by 1e-4 s, as the cull widens 0.075 to 0.0751
-  std::vector<double> VW(2 * n0);
-  for (size_t j = 0; j < n0; ++j) {
-    const double m = clr_mid((unsigned)j, 0ull, 0, w, td), h = clr_half_width(w, 0);
-    double b2[2];
-    svsdf_traj::motion_bounds(N, coeffs, S.data(), m - h - 1e-4, m + h + 1e-4, b2);
-    VW[j] = b2[0];
-    VW[n0 + j] = b2[1];
-  }
+  // level-0 motion bounds (and schedule bounds): the interval widened by 1e-4 s, as the cull widens 0.075 to 0.0751
+  const std::vector<double> VW = interval_bounds(ctx, N, coeffs, S, n0, w);
   const unsigned maxgrid = (unsigned)std::max(1, ctx->n_cu) * 8u;
   Buf<double> d_vw;
   Buf<Pose> d_mid;
@@ -75,7 +98,7 @@ int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double
   PinBuf<ClrRecord> h_rec;
   Buf<unsigned long long> d_count;
   Buf<ClrTilePair> d_tp, d_seed;
-  int rc = d_vw.alloc(ctx, 2 * n0);
+  int rc = d_vw.alloc(ctx, VW.size());
   if (rc == SVSDF_OK) rc = d_mid.alloc(ctx, n0);
   if (rc == SVSDF_OK) rc = d_orig.alloc(ctx, P);
   if (rc == SVSDF_OK) rc = d_tiles.alloc(ctx, ntiles);
@@ -86,7 +109,11 @@ int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double
   if (rc == SVSDF_OK) rc = d_seed.alloc(ctx, 1);
   if (rc) return rc;
   const double *d_V = d_vw.get(), *d_W = d_vw.get() + n0;
-  HIPCHK_AS(who, hipMemcpyAsync(d_vw, VW.data(), 2 * n0 * sizeof(double), hipMemcpyHostToDevice, st));
+  // under a scale schedule: the schedule with Imax_j, Q_j for the level kernels, Smin_j, Smax_j for the cheap bound
+  const double *const d_sb = ctx->scaled ? d_vw.get() + 2 * n0 : nullptr;   // (the rigid buffer ends after W_j)
+  const ClrScale cscale{ctx->scale, d_sb, d_sb ? d_sb + n0 : nullptr};
+  const double *d_Smin = d_sb ? d_sb + 2 * n0 : nullptr, *d_Smax = d_sb ? d_sb + 3 * n0 : nullptr;
+  HIPCHK_AS(who, hipMemcpyAsync(d_vw, VW.data(), VW.size() * sizeof(double), hipMemcpyHostToDevice, st));
   HIPCHK_AS(who, hipMemcpyAsync(d_orig, ctx->shard_idx.data(), (size_t)P * sizeof(long long), hipMemcpyHostToDevice, st));
   const size_t traj_lds = (size_t)traj_lds_doubles(N) * sizeof(double);
   hipLaunchKernelGGL(k_clr_tiles, dim3((ntiles + kClrBlock - 1) / kClrBlock), dim3(kClrBlock), 0, st, ctx->d_px.get(), ctx->d_py.get(), P,
@@ -109,11 +136,12 @@ int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double
   // broad phase: the pair with the smallest cheap bound is evaluated first and gives the first upper
   HIPCHK_AS(who, hipMemsetAsync(d_rec, 0, sizeof(ClrRecord), st));
   hipLaunchKernelGGL(k_clr_broad, dim3(broad_grid), dim3(kClrBlock), 0, st, d_tiles.get(), ntiles, d_mid.get(), d_V, (unsigned)n0, w,
-                     ctx->r_bound, 0.0, (ClrTilePair *)nullptr, 0ull, (unsigned long long *)nullptr, d_partials.get());
+                     ctx->r_bound, 0.0, (ClrTilePair *)nullptr, 0ull, (unsigned long long *)nullptr, d_partials.get(), d_Smin, d_Smax);
   if ((rc = read_record(broad_grid))) return rc;
   ClrLaunch a{};
   a.traj = ctx->d_traj; a.sp = ctx->sp; a.px = ctx->d_px; a.py = ctx->d_py; a.orig = d_orig; a.P = P; a.mid = d_mid;
   a.V = d_V; a.W = d_W; a.w = w; a.dur = td; a.rec = d_rec; a.partials = d_partials;
+  a.scl = ctx->scaled ? &cscale : nullptr;
   auto launch = [&](unsigned grid) -> int {
     if (!launch_k_clr(ctx->cfg.shape_id, grid, traj_lds, st, a))
       return fail(ctx, SVSDF_ERR_INVALID, std::string(who) + ": shape not compiled into this build");
@@ -136,7 +164,7 @@ int min_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const double
   for (int pass = 0; pass < 2; ++pass) {
     HIPCHK_AS(who, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_clr_broad, dim3(broad_grid), dim3(kClrBlock), 0, st, d_tiles.get(), ntiles, d_mid.get(), d_V, (unsigned)n0, w,
-                       ctx->r_bound, best.f, pass ? d_tp.get() : (ClrTilePair *)nullptr, kept, d_count.get(), d_partials.get());
+                       ctx->r_bound, best.f, pass ? d_tp.get() : (ClrTilePair *)nullptr, kept, d_count.get(), d_partials.get(), d_Smin, d_Smax);
     HIPCHK_AS(who, hipGetLastError());
     unsigned long long c = 0;
     HIPCHK_AS(who, hipMemcpyAsync(&c, d_count.get(), sizeof(c), hipMemcpyDeviceToHost, st));
@@ -270,14 +298,7 @@ int point_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const doub
   if (cap > ((size_t)1 << 30)) return fail(ctx, SVSDF_ERR_INVALID, std::string(who) + ": pair_capacity above 2^30");
   const unsigned long long budget = prm.max_evals ? prm.max_evals : 4ull * P * (unsigned long long)std::ceil(td / 0.15);
 
-  std::vector<double> VW(2 * n0);   // the sibling's V_j, W_j
-  for (size_t j = 0; j < n0; ++j) {
-    const double m = clr_mid((unsigned)j, 0ull, 0, w, td), h = clr_half_width(w, 0);
-    double b2[2];
-    svsdf_traj::motion_bounds(N, coeffs, S.data(), m - h - 1e-4, m + h + 1e-4, b2);
-    VW[j] = b2[0];
-    VW[n0 + j] = b2[1];
-  }
+  const std::vector<double> VW = interval_bounds(ctx, N, coeffs, S, n0, w);   // the sibling's V_j, W_j (Imax_j, Q_j, Smin_j, Smax_j)
   const unsigned maxgrid = (unsigned)std::max(1, ctx->n_cu) * 8u;
   const size_t tiles64 = (size_t)ntiles * kClrTile, n_ev = std::max(cap, tiles64);
   Buf<double> d_vw, d_tmax, d_res;
@@ -291,7 +312,7 @@ int point_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const doub
   Buf<ClrTilePair> d_tp, d_seed;
   PinBuf<double> h_res;
   PinBuf<unsigned char> h_state;
-  int rc = d_vw.alloc(ctx, 2 * n0);
+  int rc = d_vw.alloc(ctx, VW.size());
   if (rc == SVSDF_OK) rc = d_mid.alloc(ctx, n0);
   if (rc == SVSDF_OK) rc = d_tiles.alloc(ctx, ntiles);
   if (rc == SVSDF_OK) rc = d_tmax.alloc(ctx, ntiles);
@@ -308,12 +329,16 @@ int point_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const doub
   if (rc == SVSDF_OK) rc = d_ev.alloc(ctx, n_ev);
   if (rc) return rc;
   const double *d_V = d_vw.get(), *d_W = d_vw.get() + n0;
+  // under a scale schedule: the schedule with Imax_j, Q_j for the level kernels, Smin_j, Smax_j for the cheap bound
+  const double *const d_sb = ctx->scaled ? d_vw.get() + 2 * n0 : nullptr;   // (the rigid buffer ends after W_j)
+  const ClrScale cscale{ctx->scale, d_sb, d_sb ? d_sb + n0 : nullptr};
+  const double *d_Smin = d_sb ? d_sb + 2 * n0 : nullptr, *d_Smax = d_sb ? d_sb + 3 * n0 : nullptr;
   PclrState ps{};
   ps.U = d_keys.get(); ps.S = ps.U + P; ps.open = ps.S + P; ps.tw = ps.open + P;
   unsigned long long *const d_snap = ps.tw + P;
   ps.snap = d_snap;
   const unsigned pgrid = std::min((P + kClrBlock - 1) / kClrBlock, maxgrid);
-  HIPCHK_AS(who, hipMemcpyAsync(d_vw, VW.data(), 2 * n0 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIPCHK_AS(who, hipMemcpyAsync(d_vw, VW.data(), VW.size() * sizeof(double), hipMemcpyHostToDevice, st));
   const size_t traj_lds = (size_t)traj_lds_doubles(N) * sizeof(double);
   hipLaunchKernelGGL(k_pclr_fill, dim3((unsigned)std::min<size_t>((5 * (size_t)P + kClrBlock - 1) / kClrBlock, maxgrid)), dim3(kClrBlock), 0, st, d_keys.get(),
                      5 * (size_t)P, kOrdKeyPosInf);
@@ -321,12 +346,13 @@ int point_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const doub
                      ntiles, d_tiles.get());
   hipLaunchKernelGGL(k_clr_mid, dim3((unsigned)((n0 + 63) / 64)), dim3(64), traj_lds, st, ctx->d_traj.get(), w, (unsigned)n0, d_mid.get());
   hipLaunchKernelGGL(k_pclr_seed, dim3((ntiles + 3) / 4), dim3(kClrBlock), 0, st, d_tiles.get(), ntiles, d_mid.get(), d_V, (unsigned)n0, w,
-                     ctx->r_bound, d_seed.get());
+                     ctx->r_bound, d_seed.get(), d_Smin, d_Smax);
   HIPCHK_AS(who, hipGetLastError());
 
   PclrLaunch a{};
   a.traj = ctx->d_traj; a.sp = ctx->sp; a.px = ctx->d_px; a.py = ctx->d_py; a.P = P; a.mid = d_mid; a.V = d_V; a.W = d_W; a.w = w;
   a.dur = td; a.rule = PclrRule{prm.eps, prm.cap, prm.target}; a.s = ps; a.ev = d_ev; a.cnt = d_cnt;
+  a.scl = ctx->scaled ? &cscale : nullptr;
   // one launch: the level kernel, the witness pass over its evaluations (n_evals entries of d_ev), one record read
   auto launch = [&](unsigned grid, unsigned n_evals) -> int {
     HIPCHK_AS(who, hipMemsetAsync(d_cnt, 0, sizeof(PclrCounters), st));
@@ -354,7 +380,8 @@ int point_clearance_leaf(svsdf_ctx *ctx, int N, const double *coeffs, const doub
   for (int pass = 0; pass < 2; ++pass) {
     HIPCHK_AS(who, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_pclr_broad, dim3(broad_grid), dim3(kClrBlock), 0, st, d_tiles.get(), ntiles, d_mid.get(), d_V, (unsigned)n0, w,
-                       ctx->r_bound, prm.cap, d_tmax.get(), pass ? d_tp.get() : (ClrTilePair *)nullptr, kept, d_count.get(), d_tdrop.get());
+                       ctx->r_bound, prm.cap, d_tmax.get(), pass ? d_tp.get() : (ClrTilePair *)nullptr, kept, d_count.get(), d_tdrop.get(),
+                       d_Smin, d_Smax);
     HIPCHK_AS(who, hipGetLastError());
     unsigned long long c = 0;
     HIPCHK_AS(who, hipMemcpyAsync(&c, d_count.get(), sizeof(c), hipMemcpyDeviceToHost, st));
@@ -474,6 +501,15 @@ int svsdf_motion_bounds(int N, const double *coeffs, const double *T, double ta,
   return SVSDF_OK;
 }
 
+int svsdf_scale_bounds(const svsdf_scale *scale, double ta, double tb, double out4[4]) {
+  if (!out4) return fail(nullptr, SVSDF_ERR_INVALID, "svsdf_scale_bounds: null argument");
+  if (!std::isfinite(ta) || !std::isfinite(tb) || tb < ta) return fail(nullptr, SVSDF_ERR_INVALID, "svsdf_scale_bounds: needs finite ta <= tb");
+  const svsdf_traj::ScaleCheck chk = svsdf_traj::check_scale(scale);
+  if (chk.code) return fail(nullptr, chk.code, std::string("svsdf_scale_bounds: ") + chk.reason);
+  svsdf_traj::scale_bounds(scale, ta, tb, out4);
+  return SVSDF_OK;
+}
+
 int svsdf_min_clearance(svsdf_ctx *ctx, int N, const double *coeffs, const double *T, const svsdf_clearance_params *params,
                         svsdf_clearance_result *out) {
   if (!ctx || !coeffs || !T || !out) return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: null argument");
@@ -491,8 +527,9 @@ int svsdf_min_clearance(svsdf_ctx *ctx, int N, const double *coeffs, const doubl
   if (!(chk.td < 3 * 1e2))
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: total duration >= 300 s (the reference's stale-duration regime)");
   svsdf_ctx *leaf = leaf_of(ctx);
-  if (ctx->scaled || leaf->scaled)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: a scale schedule is set (the bound is the rigid one)");
+  if ((ctx->scaled || leaf->scaled) && !(ctx->cfg.flags & SVSDF_FLAG_SCALED_CLEARANCE))
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: a scale schedule is set and the context was created without "
+                                        "SVSDF_FLAG_SCALED_CLEARANCE (the bound is the rigid one)");
   if (!leaf->lipschitz_ok)
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_min_clearance: the shape SDF failed the context's Lipschitz self-check");
   if (ctx->subs.empty()) return min_clearance_leaf(ctx, N, coeffs, T, prm, out);
@@ -560,8 +597,9 @@ int svsdf_point_clearance(svsdf_ctx *ctx, int N, const double *coeffs, const dou
   if (!(chk.td < 3 * 1e2))
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_point_clearance: total duration >= 300 s (the reference's stale-duration regime)");
   svsdf_ctx *leaf = leaf_of(ctx);
-  if (ctx->scaled || leaf->scaled)
-    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_point_clearance: a scale schedule is set (the bound is the rigid one)");
+  if ((ctx->scaled || leaf->scaled) && !(ctx->cfg.flags & SVSDF_FLAG_SCALED_CLEARANCE))
+    return fail(ctx, SVSDF_ERR_INVALID, "svsdf_point_clearance: a scale schedule is set and the context was created without "
+                                        "SVSDF_FLAG_SCALED_CLEARANCE (the bound is the rigid one)");
   if (!leaf->lipschitz_ok)
     return fail(ctx, SVSDF_ERR_INVALID, "svsdf_point_clearance: the shape SDF failed the context's Lipschitz self-check");
   if (ctx->subs.empty()) return point_clearance_leaf(ctx, N, coeffs, T, prm, lower, upper, t_witness, state, out);

@@ -15,6 +15,7 @@
 //                  list of the pairs a threshold keeps
 //   k_clr_level0<SHAPE>  one wave per kept (tile, interval): transform + shape SDF against the midpoint's pose
 //   k_clr_level<SHAPE>   one lane per (point, interval) pair of a deeper level: pose_at + sdf_from_pose
+//                        (each with a scaled instantiation, Scl = ClrScale: scale_inv + rel_scaled + shape_sdf, clr_lower_sc)
 //   k_clr_reduce   fixed-order reduction of the blocks' partial results into one record the host reads
 // A level's pruning threshold is a kernel argument, fixed by the host before the level starts; the only atomics are the
 // integer slot counters of the compaction, so the SET of pairs a level emits, and with it every reported number, does not
@@ -58,6 +59,50 @@ __host__ __device__ __forceinline__ double clr_mid(unsigned j, unsigned long lon
 // the lane's lower bound over its interval: the allowance convention of the exact cull (upload_traj)
 __device__ __forceinline__ double clr_lower(double f, double h, double V, double W, double D) {
   return f - (h * (V + W * D) * (1.0 + 1e-9) + 1e-9);
+}
+
+// ---- under a scale schedule (SVSDF_FLAG_SCALED_CLEARANCE; DESIGN.md §4e "Under a scale schedule"): the value is
+// getSDFAtTimeStamp<true>, sdf(u(t)) with u(t) = R(t)^T S(t)^-1 (p - x(t)) (rel_scaled), and on the interval
+//   sdf_sc(p, t) >= sdf_sc(p, m) - h (V Imax + W |u(m)| + Q |p - x(m)|)
+// with Imax >= 1 / s_a(t) and Q >= |s_a'(t)| / s_a(t)^2 over the level-0 interval (svsdf_scale_bounds, inherited like V, W).
+// The level kernels take the schedule as the parameter pack `Scl... scl_arg` of svsdf_kernels.hpp's ScaleArg idiom: empty
+// for the rigid kernel, whose arguments and bits are then exactly those of a kernel without it, and exactly ClrScale -- the
+// ScaleDev with the two per-interval arrays of the bound -- for the scaled one.
+struct ClrScale { ScaleDev scl; const double *Imax, *Q; };
+template <typename... Scl>
+struct ClrScaleArg {
+  static_assert(sizeof...(Scl) == 0, "the scale pack is empty (rigid kernel) or exactly ClrScale (scaled kernel)");
+  static constexpr bool SC = false;
+  static __device__ __forceinline__ ClrScale get() { return ClrScale{}; }
+};
+template <>
+struct ClrScaleArg<ClrScale> {
+  static constexpr bool SC = true;
+  static __device__ __forceinline__ const ClrScale &get(const ClrScale &s) { return s; }
+};
+// U = |u(m)|, the norm of the rel_scaled output; Imax = 1, Q = 0, U = D is clr_lower
+__device__ __forceinline__ double clr_lower_sc(double f, double h, double V, double W, double Imax, double Q, double D, double U) {
+  return f - (h * (V * Imax + W * U + Q * D) * (1.0 + 1e-9) + 1e-9);
+}
+// One evaluation against pose p at time t and its bound over the half width h: the rigid pair (sdf_from_pose, clr_lower)
+// or the scaled one (scale_inv, rel_scaled, shape_sdf: sdf_at_sc's value bit for bit; clr_lower_sc).
+template <int SHAPE, bool SC>
+__device__ __forceinline__ double clr_eval(const ShapeParams &sp, const ClrScale &cs, const Pose &p, double px, double py, double t,
+                                           double h, const double *__restrict__ V_, const double *__restrict__ W_, unsigned j,
+                                           double &lb) {
+  const double dx = px - p.x, dy = py - p.y;
+  if constexpr (SC) {
+    double i00, i11, rx, ry;
+    scale_inv(cs.scl, t, i00, i11);
+    rel_scaled(p, px, py, i00, i11, rx, ry);
+    const double f = shape_sdf<SHAPE>(sp, rx, ry);
+    lb = clr_lower_sc(f, h, V_[j], W_[j], cs.Imax[j], cs.Q[j], sqrt(dx * dx + dy * dy), sqrt(rx * rx + ry * ry));
+    return f;
+  } else {
+    const double f = sdf_from_pose<SHAPE>(sp, p, px, py);
+    lb = clr_lower(f, h, V_[j], W_[j], sqrt(dx * dx + dy * dy));
+    return f;
+  }
 }
 
 // block-wide fixed-order reduction of the lanes' partials; thread 0 writes the block's
@@ -107,12 +152,14 @@ __device__ __forceinline__ void clr_settle_or_split(ClrPartial &mine, double lb,
 
 // Level 0: wave v of the launch takes (tile, interval) pair tp[v], lane l the tile's point l.  The value is
 // sdf_from_pose against the midpoint's pose from k_clr_mid, i.e. pose_at's pose: bit for bit sdf_at(p, m).
-template <int SHAPE>
+template <int SHAPE, typename... Scl>
 __global__ void __launch_bounds__(kClrBlock)
 k_clr_level0(ShapeParams sp, const double *__restrict__ px_, const double *__restrict__ py_, const long long *__restrict__ orig,
              unsigned P, const Pose *__restrict__ mid, const double *__restrict__ V_, const double *__restrict__ W_, double w,
              double dur, const ClrTilePair *__restrict__ tp, unsigned ntp, double thr, int emit, ClrPair *__restrict__ out,
-             unsigned out_cap, ClrRecord *__restrict__ rec, ClrPartial *__restrict__ partials) {
+             unsigned out_cap, ClrRecord *__restrict__ rec, ClrPartial *__restrict__ partials, Scl... scl_arg) {
+  constexpr bool SC = ClrScaleArg<Scl...>::SC;
+  const ClrScale cs = ClrScaleArg<Scl...>::get(scl_arg...);
   ClrPartial mine = clr_no_partial();
   const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = kClrBlock / 64;
   const double h = clr_half_width(w, 0);
@@ -122,25 +169,27 @@ k_clr_level0(ShapeParams sp, const double *__restrict__ px_, const double *__res
     if (pt >= P) continue;
     const Pose p = mid[q.j];
     const double px = px_[pt], py = py_[pt];
-    const double f = sdf_from_pose<SHAPE>(sp, p, px, py);
+    const double t = clr_mid(q.j, 0ull, 0, w, dur);
+    double lb;
+    const double f = clr_eval<SHAPE, SC>(sp, cs, p, px, py, t, h, V_, W_, q.j, lb);
     ClrBest b;
-    b.f = f; b.idx = orig[pt]; b.t = clr_mid(q.j, 0ull, 0, w, dur); b.pt = pt; b.pad_ = 0u;
+    b.f = f; b.idx = orig[pt]; b.t = t; b.pt = pt; b.pad_ = 0u;
     if (clr_better(b, mine.best)) mine.best = b;
     mine.evals += 1ull;
-    const double dx = px - p.x, dy = py - p.y;
-    const double lb = clr_lower(f, h, V_[q.j], W_[q.j], sqrt(dx * dx + dy * dy));
     clr_settle_or_split(mine, lb, thr, emit, pt, q.j, 0ull, out, out_cap, rec);
   }
   clr_block_reduce(mine, partials);
 }
 
 // Level L >= 1: lane per pair, the evaluation of k_debug_sdf_at (pose_at, sdf_from_pose, the context's piece-time mode).
-template <int SHAPE>
+template <int SHAPE, typename... Scl>
 __global__ void __launch_bounds__(kClrBlock)
 k_clr_level(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__restrict__ px_, const double *__restrict__ py_,
             const long long *__restrict__ orig, const double *__restrict__ V_, const double *__restrict__ W_, double w, int L,
             const ClrPair *__restrict__ in, unsigned n, double thr, ClrPair *__restrict__ out, unsigned out_cap,
-            ClrRecord *__restrict__ rec, ClrPartial *__restrict__ partials) {
+            ClrRecord *__restrict__ rec, ClrPartial *__restrict__ partials, Scl... scl_arg) {
+  constexpr bool SC = ClrScaleArg<Scl...>::SC;
+  const ClrScale cs = ClrScaleArg<Scl...>::get(scl_arg...);
   extern __shared__ double clr_lds[];
   const TrajL tr = stage_traj(trg, clr_lds);
   ClrPartial mine = clr_no_partial();
@@ -151,13 +200,12 @@ k_clr_level(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__res
     const double t = clr_mid(q.j, q.k, L, w, tr.dur);
     const Pose p = pose_at(tr, t, pc);
     const double px = px_[q.pt], py = py_[q.pt];
-    const double f = sdf_from_pose<SHAPE>(sp, p, px, py);
+    double lb;
+    const double f = clr_eval<SHAPE, SC>(sp, cs, p, px, py, t, h, V_, W_, q.j, lb);
     ClrBest b;
     b.f = f; b.idx = orig[q.pt]; b.t = t; b.pt = q.pt; b.pad_ = 0u;
     if (clr_better(b, mine.best)) mine.best = b;
     mine.evals += 1ull;
-    const double dx = px - p.x, dy = py - p.y;
-    const double lb = clr_lower(f, h, V_[q.j], W_[q.j], sqrt(dx * dx + dy * dy));
     clr_settle_or_split(mine, lb, thr, 1, q.pt, q.j, q.k, out, out_cap, rec);
   }
   clr_block_reduce(mine, partials);
@@ -219,12 +267,14 @@ __device__ __forceinline__ void pclr_count_evals(unsigned long long evals, PclrC
 }
 
 // Level 0 and the seed (`emit == 0`: values only): k_clr_level0's wave per (tile, interval), evaluation v * 64 + lane.
-template <int SHAPE>
+template <int SHAPE, typename... Scl>
 __global__ void __launch_bounds__(kClrBlock)
 k_pclr_level0(ShapeParams sp, const double *__restrict__ px_, const double *__restrict__ py_, unsigned P,
               const Pose *__restrict__ mid, const double *__restrict__ V_, const double *__restrict__ W_, double w, double dur,
               const ClrTilePair *__restrict__ tp, unsigned ntp, PclrRule rule, int emit, PclrState s, PclrEval *__restrict__ ev,
-              ClrPair *__restrict__ out, unsigned out_cap, PclrCounters *__restrict__ cnt) {
+              ClrPair *__restrict__ out, unsigned out_cap, PclrCounters *__restrict__ cnt, Scl... scl_arg) {
+  constexpr bool SC = ClrScaleArg<Scl...>::SC;
+  const ClrScale cs = ClrScaleArg<Scl...>::get(scl_arg...);
   const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, waves = kClrBlock / 64;
   const double h = clr_half_width(w, 0);
   unsigned long long evals = 0ull;
@@ -234,27 +284,29 @@ k_pclr_level0(ShapeParams sp, const double *__restrict__ px_, const double *__re
     if (pt >= P) continue;
     const Pose p = mid[q.j];
     const double px = px_[pt], py = py_[pt];
-    const double f = sdf_from_pose<SHAPE>(sp, p, px, py);
     PclrEval e;
-    e.f = f; e.t = clr_mid(q.j, 0ull, 0, w, dur);
+    e.t = clr_mid(q.j, 0ull, 0, w, dur);
+    double lb;
+    const double f = clr_eval<SHAPE, SC>(sp, cs, p, px, py, e.t, h, V_, W_, q.j, lb);
+    e.f = f;
     ev[(size_t)v * kClrTile + lane] = e;
     evals += 1ull;
     pclr_value(s, pt, f);
     if (!emit) continue;
-    const double dx = px - p.x, dy = py - p.y;
-    const double lb = clr_lower(f, h, V_[q.j], W_[q.j], sqrt(dx * dx + dy * dy));
     pclr_settle_or_split(lb, rule, s, pt, q.j, 0ull, out, out_cap, cnt);
   }
   pclr_count_evals(evals, cnt);
 }
 
 // Level L >= 1: k_clr_level's lane per pair, evaluation i beside pair i.
-template <int SHAPE>
+template <int SHAPE, typename... Scl>
 __global__ void __launch_bounds__(kClrBlock)
 k_pclr_level(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__restrict__ px_, const double *__restrict__ py_,
              const double *__restrict__ V_, const double *__restrict__ W_, double w, int L, const ClrPair *__restrict__ in,
              unsigned n, PclrRule rule, PclrState s, PclrEval *__restrict__ ev, ClrPair *__restrict__ out, unsigned out_cap,
-             PclrCounters *__restrict__ cnt) {
+             PclrCounters *__restrict__ cnt, Scl... scl_arg) {
+  constexpr bool SC = ClrScaleArg<Scl...>::SC;
+  const ClrScale cs = ClrScaleArg<Scl...>::get(scl_arg...);
   extern __shared__ double clr_lds[];
   const TrajL tr = stage_traj(trg, clr_lds);
   const double h = clr_half_width(w, L);
@@ -265,14 +317,13 @@ k_pclr_level(const TrajDev *__restrict__ trg, ShapeParams sp, const double *__re
     const double t = clr_mid(q.j, q.k, L, w, tr.dur);
     const Pose p = pose_at(tr, t, pc);
     const double px = px_[q.pt], py = py_[q.pt];
-    const double f = sdf_from_pose<SHAPE>(sp, p, px, py);
+    double lb;
+    const double f = clr_eval<SHAPE, SC>(sp, cs, p, px, py, t, h, V_, W_, q.j, lb);
     PclrEval e;
     e.f = f; e.t = t;
     ev[i] = e;
     evals += 1ull;
     pclr_value(s, q.pt, f);
-    const double dx = px - p.x, dy = py - p.y;
-    const double lb = clr_lower(f, h, V_[q.j], W_[q.j], sqrt(dx * dx + dy * dy));
     pclr_settle_or_split(lb, rule, s, q.pt, q.j, q.k, out, out_cap, cnt);
   }
   pclr_count_evals(evals, cnt);
@@ -321,18 +372,37 @@ __device__ __forceinline__ double clr_cheap(const ClrTileCircle c, const Pose p,
   return sqrt(dx * dx + dy * dy) * (1.0 - 1e-12) - c.r - r_bound - (h * V * (1.0 + 1e-9) + 1e-9);
 }
 
+// Under a scale schedule (Smin_ / Smax_ not null: the per-interval bounds of s_a): with num = |c_tile - x(m)| - r_tile - h V,
+// every point of the tile has |p - x(t)| >= num, |u| = |S^-1 (p - x)| >= |p - x| / Smax and sdf(u) >= |u| - r_bound, so
+// num / Smax - r_bound bounds the tile from below when num >= 0.  When num < 0 the tile may reach the pose and -r_bound is
+// all that holds; ANY value at or below it is a valid bound, and which one only orders the overlapping pairs -- that is, it
+// picks the seed.  num Smin - r_bound ranks them by how deep the overlap is in the world times the smallest scale of the
+// interval: a tile deep inside a LARGE robot first, where one of its points is likeliest to be interior and to give a first
+// upper near the minimum (dividing by Smin instead would put the intervals where the robot is smallest first).
+__device__ __forceinline__ double clr_cheap_sc(const ClrTileCircle c, const Pose p, double h, double V, double r_bound, double Smin,
+                                               double Smax) {
+  const double dx = c.cx - p.x, dy = c.cy - p.y;
+  const double num = sqrt(dx * dx + dy * dy) * (1.0 - 1e-12) - c.r - (h * V * (1.0 + 1e-9) + 1e-9);
+  return (num >= 0.0 ? num / Smax * (1.0 - 1e-12) : num * Smin) - r_bound;
+}
+__device__ __forceinline__ double clr_cheap_any(const ClrTileCircle c, const Pose p, double h, double V, double r_bound,
+                                                const double *__restrict__ Smin_, const double *__restrict__ Smax_, unsigned j) {
+  return Smax_ ? clr_cheap_sc(c, p, h, V, r_bound, Smin_[j], Smax_[j]) : clr_cheap(c, p, h, V, r_bound);
+}
+
 // list == null, count == null: the minimum of the cheap bound (ties: the smallest pair index) as block partials.
 // count != null: the pairs with cheap <= thr are counted, and written to `list` when there is one (cap entries).
 __global__ void __launch_bounds__(kClrBlock)
 k_clr_broad(const ClrTileCircle *__restrict__ tiles, unsigned ntiles, const Pose *__restrict__ mid, const double *__restrict__ V_,
             unsigned n0, double w, double r_bound, double thr, ClrTilePair *__restrict__ list, unsigned long long cap,
-            unsigned long long *__restrict__ count, ClrPartial *__restrict__ partials) {
+            unsigned long long *__restrict__ count, ClrPartial *__restrict__ partials, const double *__restrict__ Smin_,
+            const double *__restrict__ Smax_) {
   ClrPartial mine = clr_no_partial();
   const double h = clr_half_width(w, 0);
   const unsigned long long total = (unsigned long long)ntiles * n0;
   for (unsigned long long i = (unsigned long long)blockIdx.x * kClrBlock + threadIdx.x; i < total; i += (unsigned long long)gridDim.x * kClrBlock) {
     const unsigned tile = (unsigned)(i / n0), j = (unsigned)(i % n0);
-    const double cheap = clr_cheap(tiles[tile], mid[j], h, V_[j], r_bound);
+    const double cheap = clr_cheap_any(tiles[tile], mid[j], h, V_[j], r_bound, Smin_, Smax_, j);
     if (count) {
       if (cheap <= thr) {
         const unsigned long long slot = atomicAdd(count, 1ull);
@@ -382,7 +452,8 @@ k_pclr_snapshot(const unsigned long long *__restrict__ U, unsigned long long *__
 // tile.  One wave per tile.
 __global__ void __launch_bounds__(kClrBlock)
 k_pclr_seed(const ClrTileCircle *__restrict__ tiles, unsigned ntiles, const Pose *__restrict__ mid, const double *__restrict__ V_,
-            unsigned n0, double w, double r_bound, ClrTilePair *__restrict__ seed) {
+            unsigned n0, double w, double r_bound, ClrTilePair *__restrict__ seed, const double *__restrict__ Smin_,
+            const double *__restrict__ Smax_) {
   const unsigned lane = threadIdx.x & 63u, tile = blockIdx.x * (kClrBlock / 64) + (threadIdx.x >> 6);
   if (tile >= ntiles) return;   // (the whole wave)
   const double h = clr_half_width(w, 0);
@@ -390,7 +461,7 @@ k_pclr_seed(const ClrTileCircle *__restrict__ tiles, unsigned ntiles, const Pose
   double best = __builtin_huge_val();
   unsigned bj = 0xffffffffu;
   for (unsigned j = lane; j < n0; j += 64u) {
-    const double cheap = clr_cheap(c, mid[j], h, V_[j], r_bound);
+    const double cheap = clr_cheap_any(c, mid[j], h, V_[j], r_bound, Smin_, Smax_, j);
     if (cheap < best || bj == 0xffffffffu) { best = cheap == cheap ? cheap : __builtin_huge_val(); bj = j; }
   }
   for (int o = 32; o > 0; o >>= 1) {
@@ -422,12 +493,13 @@ k_pclr_tile_max(const unsigned long long *__restrict__ U, unsigned P, unsigned n
 __global__ void __launch_bounds__(kClrBlock)
 k_pclr_broad(const ClrTileCircle *__restrict__ tiles, unsigned ntiles, const Pose *__restrict__ mid, const double *__restrict__ V_,
              unsigned n0, double w, double r_bound, double cap, const double *__restrict__ tmax, ClrTilePair *__restrict__ list,
-             unsigned long long cap_entries, unsigned long long *__restrict__ count, unsigned long long *__restrict__ tdrop) {
+             unsigned long long cap_entries, unsigned long long *__restrict__ count, unsigned long long *__restrict__ tdrop,
+             const double *__restrict__ Smin_, const double *__restrict__ Smax_) {
   const double h = clr_half_width(w, 0);
   const unsigned long long total = (unsigned long long)ntiles * n0;
   for (unsigned long long i = (unsigned long long)blockIdx.x * kClrBlock + threadIdx.x; i < total; i += (unsigned long long)gridDim.x * kClrBlock) {
     const unsigned tile = (unsigned)(i / n0), j = (unsigned)(i % n0);
-    const double cheap = clr_cheap(tiles[tile], mid[j], h, V_[j], r_bound);
+    const double cheap = clr_cheap_any(tiles[tile], mid[j], h, V_[j], r_bound, Smin_, Smax_, j);
     const double tm = tmax[tile], thr = cap < tm ? cap : tm;
     if (!(cheap > thr)) {
       const unsigned long long slot = atomicAdd(count, 1ull);

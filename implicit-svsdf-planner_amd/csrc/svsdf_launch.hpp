@@ -41,19 +41,22 @@ struct ClrLaunch {     // arguments of k_clr_level0<SHAPE> (L == 0: tp / ntp, mi
   const TrajDev *traj; ShapeParams sp; const double *px, *py; const long long *orig; unsigned P; const Pose *mid;
   const double *V, *W; double w, dur; int L; const ClrTilePair *tp; const ClrPair *in; unsigned n; double thr; int emit;
   ClrPair *out; unsigned out_cap; ClrRecord *rec; ClrPartial *partials;
+  const ClrScale *scl = nullptr;   // not null: k_clr_level0 / k_clr_level<SHAPE, ClrScale> under this schedule and its per-interval bounds
 };
 struct PclrLaunch {    // arguments of k_pclr_level0<SHAPE> (L == 0: tp / ntp, mid, emit) and k_pclr_level<SHAPE> (L >= 1: traj, in / n)
   const TrajDev *traj; ShapeParams sp; const double *px, *py; unsigned P; const Pose *mid; const double *V, *W; double w, dur;
   int L; const ClrTilePair *tp; const ClrPair *in; unsigned n; PclrRule rule; int emit; PclrState s; PclrEval *ev;
   ClrPair *out; unsigned out_cap; PclrCounters *cnt;
+  const ClrScale *scl = nullptr;   // not null: k_pclr_level0 / k_pclr_level<SHAPE, ClrScale>
 };
 // lane-group widths the scaled solve is instantiated for (§4c: a reduced plan space); scaled_lanes maps any width onto them
 constexpr int kScaledLanes[3] = {4, 8, 32};
 inline int scaled_lanes(int G) { return G >= 32 ? 32 : G >= 8 ? 8 : 4; }
-// The rigid / scaled choice of a launch site: f() for the rigid kernel, f(*scl) under a scale schedule.  A generic lambda
+// The rigid / scaled choice of a launch site: f() for the rigid kernel, f(*scl) under a scale schedule (S: ScaleDev, or the
+// clearance kernels' ClrScale).  A generic lambda
 // `[&](auto... scl)` then holds ONE launch expression for both: k_x<..., decltype(scl)...> with `scl...` among its arguments.
-template <typename F>
-auto with_scale(const ScaleDev *scl, F &&f) { return scl ? f(*scl) : f(); }
+template <typename S, typename F>
+auto with_scale(const S *scl, F &&f) { return scl ? f(*scl) : f(); }
 
 // each returns false when the shape id is not compiled into the library (development builds)
 bool launch_k_solve(int shape, int G, unsigned grid, unsigned block, size_t lds, hipStream_t st, const SolveLaunch &a);

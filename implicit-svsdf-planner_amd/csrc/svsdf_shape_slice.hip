@@ -2,8 +2,9 @@
 //
 // Slice k instantiates k_solve / k_round / k_tail / k_classify / k_rbound / k_subsw / k_shape_kernels / k_succ /
 // k_astar / k_debug_sdf_at / k_clr_level0 / k_clr_level / k_pclr_level0 / k_pclr_level for the shapes with id % 4 == k and exports the launchers svsdf_pipeline.hip dispatches to
-// (svsdf_launch.hpp).  k_solve, k_classify and k_debug_sdf_at are each one template with a rigid and a scaled instantiation
-// (an empty parameter pack or ScaleDev, svsdf_kernels.hpp ScaleArg); with_scale picks between them at the one place each is
+// (svsdf_launch.hpp).  k_solve, k_classify, k_debug_sdf_at and the four clearance level kernels are each one template with a
+// rigid and a scaled instantiation (an empty parameter pack or ScaleDev, svsdf_kernels.hpp ScaleArg; ClrScale for the clearance
+// kernels, svsdf_clearance.hpp); with_scale picks between them at the one place each is
 // launched.  Splitting the ~580 kernel instantiations over four translation units lets the build run in parallel (one TU
 // took 140 s).
 #include <hip/hip_runtime.h>
@@ -184,18 +185,21 @@ bool debug_sdf_at_s(unsigned grid, size_t lds, hipStream_t st, const TrajDev *tr
   }
 }
 
-// svsdf_min_clearance (svsdf_clearance.hpp): level 0 against the midpoint pose table, deeper levels through pose_at
+// svsdf_min_clearance (svsdf_clearance.hpp): level 0 against the midpoint pose table, deeper levels through pose_at; under a
+// scale schedule (a.scl) the scaled instantiations
 template <int S>
 bool clr_s(unsigned grid, size_t lds, hipStream_t st, const ClrLaunch &a) {
   if constexpr (!shape_enabled<S>()) {
     return false;
   } else {
-    if (a.L == 0)
-      hipLaunchKernelGGL((k_clr_level0<S>), dim3(grid), dim3(kClrBlock), 0, st, a.sp, a.px, a.py, a.orig, a.P, a.mid, a.V, a.W, a.w,
-                         a.dur, a.tp, a.n, a.thr, a.emit, a.out, a.out_cap, a.rec, a.partials);
-    else
-      hipLaunchKernelGGL((k_clr_level<S>), dim3(grid), dim3(kClrBlock), lds, st, a.traj, a.sp, a.px, a.py, a.orig, a.V, a.W, a.w, a.L,
-                         a.in, a.n, a.thr, a.out, a.out_cap, a.rec, a.partials);
+    with_scale(a.scl, [&](auto... scl) {
+      if (a.L == 0)
+        hipLaunchKernelGGL((k_clr_level0<S, decltype(scl)...>), dim3(grid), dim3(kClrBlock), 0, st, a.sp, a.px, a.py, a.orig, a.P, a.mid,
+                           a.V, a.W, a.w, a.dur, a.tp, a.n, a.thr, a.emit, a.out, a.out_cap, a.rec, a.partials, scl...);
+      else
+        hipLaunchKernelGGL((k_clr_level<S, decltype(scl)...>), dim3(grid), dim3(kClrBlock), lds, st, a.traj, a.sp, a.px, a.py, a.orig,
+                           a.V, a.W, a.w, a.L, a.in, a.n, a.thr, a.out, a.out_cap, a.rec, a.partials, scl...);
+    });
     return true;
   }
 }
@@ -206,12 +210,14 @@ bool pclr_s(unsigned grid, size_t lds, hipStream_t st, const PclrLaunch &a) {
   if constexpr (!shape_enabled<S>()) {
     return false;
   } else {
-    if (a.L == 0)
-      hipLaunchKernelGGL((k_pclr_level0<S>), dim3(grid), dim3(kClrBlock), 0, st, a.sp, a.px, a.py, a.P, a.mid, a.V, a.W, a.w, a.dur,
-                         a.tp, a.n, a.rule, a.emit, a.s, a.ev, a.out, a.out_cap, a.cnt);
-    else
-      hipLaunchKernelGGL((k_pclr_level<S>), dim3(grid), dim3(kClrBlock), lds, st, a.traj, a.sp, a.px, a.py, a.V, a.W, a.w, a.L, a.in,
-                         a.n, a.rule, a.s, a.ev, a.out, a.out_cap, a.cnt);
+    with_scale(a.scl, [&](auto... scl) {
+      if (a.L == 0)
+        hipLaunchKernelGGL((k_pclr_level0<S, decltype(scl)...>), dim3(grid), dim3(kClrBlock), 0, st, a.sp, a.px, a.py, a.P, a.mid, a.V,
+                           a.W, a.w, a.dur, a.tp, a.n, a.rule, a.emit, a.s, a.ev, a.out, a.out_cap, a.cnt, scl...);
+      else
+        hipLaunchKernelGGL((k_pclr_level<S, decltype(scl)...>), dim3(grid), dim3(kClrBlock), lds, st, a.traj, a.sp, a.px, a.py, a.V,
+                           a.W, a.w, a.L, a.in, a.n, a.rule, a.s, a.ev, a.out, a.out_cap, a.cnt, scl...);
+    });
     return true;
   }
 }

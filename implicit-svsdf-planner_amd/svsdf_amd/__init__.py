@@ -7,13 +7,13 @@ library or a GPU is missing.
 """
 from .binding import (SHAPES, SHAPE_ID, SvsdfError, SvsdfContext, lib, lib_path, minco_coeffs,
                       forward_T, backward_T, shape_id_from_inputdata, shard_plan,
-                      FLAG_HOST_ONLY, FLAG_KEEP_INPUT_ORDER, FLAG_EXACT_PIECE_TIME, FLAG_FAST_PIECE_TIME, FLAG_POLYGON_YAW_KERNELS, OccupancyMap, lbfgs_minimize, lbfgs_params,
-                      LBFGS_STATUS, sum_partials, COMBINE_AUTO, COMBINE_HOST, COMBINE_RCCL, mesh_outline, mesh_outline_obj, outline_extrude, mesh_section, mesh_section_obj, kernel_bfs, live_allocations, path_waypoints, motion_bounds, CLEARANCE_STATUS, POINT_STATE)
+                      FLAG_HOST_ONLY, FLAG_KEEP_INPUT_ORDER, FLAG_EXACT_PIECE_TIME, FLAG_FAST_PIECE_TIME, FLAG_POLYGON_YAW_KERNELS, FLAG_SCALED_CLEARANCE, OccupancyMap, lbfgs_minimize, lbfgs_params,
+                      LBFGS_STATUS, sum_partials, COMBINE_AUTO, COMBINE_HOST, COMBINE_RCCL, mesh_outline, mesh_outline_obj, outline_extrude, mesh_section, mesh_section_obj, kernel_bfs, live_allocations, path_waypoints, motion_bounds, scale_bounds, CLEARANCE_STATUS, POINT_STATE)
 from .traj_optimizer import TrajOptimizer
 from . import workload
 
 __all__ = ["SHAPES", "SHAPE_ID", "SvsdfError", "SvsdfContext", "TrajOptimizer", "lib", "lib_path",
            "minco_coeffs", "forward_T", "backward_T", "shape_id_from_inputdata", "shard_plan",
-           "FLAG_HOST_ONLY", "FLAG_KEEP_INPUT_ORDER", "FLAG_EXACT_PIECE_TIME", "FLAG_FAST_PIECE_TIME", "FLAG_POLYGON_YAW_KERNELS", "OccupancyMap", "workload", "lbfgs_minimize",
+           "FLAG_HOST_ONLY", "FLAG_KEEP_INPUT_ORDER", "FLAG_EXACT_PIECE_TIME", "FLAG_FAST_PIECE_TIME", "FLAG_POLYGON_YAW_KERNELS", "FLAG_SCALED_CLEARANCE", "OccupancyMap", "workload", "lbfgs_minimize",
            "lbfgs_params", "LBFGS_STATUS", "sum_partials", "COMBINE_AUTO", "COMBINE_HOST", "COMBINE_RCCL",
-           "mesh_outline", "mesh_outline_obj", "outline_extrude", "mesh_section", "mesh_section_obj", "kernel_bfs", "live_allocations", "path_waypoints", "motion_bounds", "CLEARANCE_STATUS", "POINT_STATE"]
+           "mesh_outline", "mesh_outline_obj", "outline_extrude", "mesh_section", "mesh_section_obj", "kernel_bfs", "live_allocations", "path_waypoints", "motion_bounds", "scale_bounds", "CLEARANCE_STATUS", "POINT_STATE"]

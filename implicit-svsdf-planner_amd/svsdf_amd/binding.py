@@ -37,7 +37,7 @@ EXPORTS = [
     "svsdf_map_build_device", "svsdf_map_device_get_info", "svsdf_map_device_cells", "svsdf_frontend_set_map_device",
     "svsdf_set_points_from_map", "svsdf_map_device_points", "svsdf_path_waypoints",
     "svsdf_clearance_params_default", "svsdf_min_clearance", "svsdf_motion_bounds",
-    "svsdf_point_clearance_params_default", "svsdf_point_clearance",
+    "svsdf_point_clearance_params_default", "svsdf_point_clearance", "svsdf_scale_bounds",
 ]
 
 
@@ -283,6 +283,7 @@ def lib():
     L.svsdf_clearance_params_default.restype = None
     L.svsdf_min_clearance.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(ClearanceParams), C.POINTER(ClearanceResult)]
     L.svsdf_motion_bounds.argtypes = [C.c_int, _dp, _dp, C.c_double, C.c_double, _dp]
+    L.svsdf_scale_bounds.argtypes = [C.POINTER(Scale), C.c_double, C.c_double, _dp]
     L.svsdf_point_clearance_params_default.argtypes = [C.POINTER(PointClearanceParams)]
     L.svsdf_point_clearance_params_default.restype = None
     L.svsdf_point_clearance.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.POINTER(PointClearanceParams), _dp, _dp, _dp,
@@ -365,6 +366,26 @@ def motion_bounds(coeffs, T, ta, tb):
     if rc:
         raise SvsdfError(f"svsdf_motion_bounds failed ({rc}): " + lib().svsdf_last_error_string(None).decode())
     return float(o[0]), float(o[1])
+
+
+def scale_bounds(schedule, ta, tb, enabled=True, struct_size=None):
+    """Rigorous (Smin, Smax, Imax, Q) of a scale schedule over [ta, tb] (svsdf_scale_bounds; host only): the smallest and
+    largest scale factor, the largest 1 / s_a and the largest |s_a'| / s_a^2.  schedule: None (the identity) or a dict
+    c / amp / omega / phase like EXAMPLE_SCALE."""
+    o = np.zeros(4)
+    ref = None
+    if schedule is not None:
+        s = Scale()
+        s.struct_size = C.sizeof(Scale) if struct_size is None else int(struct_size)
+        s.enabled = int(bool(enabled))
+        for name in ("c", "amp", "omega", "phase"):
+            v = schedule.get(name, (1.0, 1.0) if name == "c" else (0.0, 0.0))
+            getattr(s, name)[:] = [float(v[0]), float(v[1])]
+        ref = C.byref(s)
+    rc = lib().svsdf_scale_bounds(ref, float(ta), float(tb), _p(o))
+    if rc:
+        raise SvsdfError(f"svsdf_scale_bounds failed ({rc}): " + lib().svsdf_last_error_string(None).decode())
+    return tuple(float(x) for x in o)
 
 
 def live_allocations():
@@ -537,6 +558,7 @@ FLAG_HOST_ONLY = 2
 FLAG_EXACT_PIECE_TIME = 4
 FLAG_FAST_PIECE_TIME = 8
 FLAG_POLYGON_YAW_KERNELS = 16   # Polygon contexts: yaw kernels and the front end (svsdf_c.h)
+FLAG_SCALED_CLEARANCE = 32      # min_clearance / point_clearance under a scale schedule (svsdf_c.h)
 COMBINE_AUTO, COMBINE_HOST, COMBINE_RCCL = 0, 1, 2
 
 
@@ -969,7 +991,8 @@ class SvsdfContext:
 
     def min_clearance(self, coeffs, T, eps=1e-3, target=None, max_evals=0, pair_capacity=0, struct_size=None):
         """Certified bracket lower <= c* <= upper on the minimum over the resident cloud and over [0, sum T] of the
-        SDF-at-time, with a witness (svsdf_min_clearance).  Returns the fields of svsdf_clearance_result as a dict
+        SDF-at-time, with a witness (svsdf_min_clearance).  Under a scale schedule (a context created with
+        FLAG_SCALED_CLEARANCE) the value is the scaled one, debug_sdf_at's under the schedule.  Returns the fields of svsdf_clearance_result as a dict
         (status as one of CLEARANCE_STATUS, point_xy as a tuple).  target=None: no target."""
         T = _f64(T)
         cm = _colmajor(coeffs)

@@ -140,6 +140,11 @@ typedef struct svsdf_config {
  * limits of svsdf_frontend_set_map, stages 0 - 4, the A* ordering, slicing, counters.  On a context of any other shape
  * the flag is accepted and has no effect. */
 #define SVSDF_FLAG_POLYGON_YAW_KERNELS 16
+/* svsdf_min_clearance and svsdf_point_clearance under a scale schedule (svsdf_set_scale).  Without this flag the two entries
+ * refuse a context with a schedule in force; with it they run the scaled search described with them (the bound of
+ * svsdf_scale_bounds).  On a context without a schedule the flag changes nothing: the rigid search, the same kernels, the
+ * same bits.  No other entry reads it. */
+#define SVSDF_FLAG_SCALED_CLEARANCE 32
 
 typedef struct svsdf_ctx svsdf_ctx;
 
@@ -542,11 +547,19 @@ int svsdf_outline_extrude(const double *xy, const int *loop_sizes, size_t n_loop
  * launch plan, svsdf_last_stats and the bits of every later evaluation as they were.  A multi-device context searches
  * every stripe on its own device; the host takes the smallest lower, the smallest upper with its witness (ties: the
  * smaller original index) and sums the counters (levels, device_ms: the largest).
+ * Under a scale schedule (svsdf_set_scale) on a context created with SVSDF_FLAG_SCALED_CLEARANCE the value is
+ * getSDFAtTimeStamp<true>(p, t) = sdf(u), u = R(t)^T S(t)^-1 (p - x(t)): the number the optimiser penalises against
+ * safety_hor, and what svsdf_debug_sdf_at returns under the schedule (the witness reproduces with it bit for bit).  Its sign
+ * is exact (p is inside the scaled robot at t iff the value is < 0); its magnitude is in SCALED BODY-FRAME units: for a
+ * positive value v the world distance from p to the robot is at least (min_a (c_a - |A_a|)) * v.  The pair's bound is then
+ *   sdf_sc(p, m) - h (V Imax + W |u(m)| + Q |p - x(m)|),   Imax, Q: the interval's svsdf_scale_bounds,
+ * and the tile test divides the circle's distance to the pose by the interval's largest scale factor.  Everything
+ * else -- intervals, levels, thresholds, budget, states, counters, the combination over devices -- is the rigid search's.
  * Returns SVSDF_ERR_NO_POINTS without a resident cloud, SVSDF_ERR_NO_DEVICE on a host-only context,
  * SVSDF_ERR_NONFINITE for a non-finite trajectory, SVSDF_ERR_INVALID with a message for a bad N, eps or struct_size, a
- * scale schedule in force (svsdf_set_scale: the bound is the rigid one), a total duration >= 300 s (the reference's
- * stale-duration regime, SWM:376-385) and a context whose Lipschitz self-check failed.  An empty resident cloud gives
- * lower = upper = +infinity and point_index = -1. */
+ * scale schedule in force on a context created without SVSDF_FLAG_SCALED_CLEARANCE (the bound is then the rigid one), a
+ * total duration >= 300 s (the reference's stale-duration regime, SWM:376-385) and a context whose Lipschitz self-check
+ * failed.  An empty resident cloud gives lower = upper = +infinity and point_index = -1. */
 typedef struct svsdf_clearance_params {
   size_t struct_size;            /* sizeof(svsdf_clearance_params) */
   double eps;                    /* > 0, finite: converged when upper - lower <= eps (default 1e-3) */
@@ -748,7 +761,9 @@ int svsdf_last_launches(const svsdf_ctx *ctx, svsdf_launch_rec *out, int cap, in
  *     (back_end_optimizer.hpp:1050, 1062).
  * getDotScale / the analytic time derivative are never read on this path (sw_manager.hpp:806).
  * Honoured by svsdf_eval_penalty(_partial), svsdf_lmbm_evaluate and the lmbm_* split, svsdf_query_points,
- * svsdf_optimize_traj, svsdf_swept_outline and svsdf_debug_sdf_at (the scaled value and body-frame point).  The front-end
+ * svsdf_optimize_traj, svsdf_swept_outline, svsdf_debug_sdf_at (the scaled value and body-frame point) and, on a context
+ * created with SVSDF_FLAG_SCALED_CLEARANCE, svsdf_min_clearance and svsdf_point_clearance (without the flag they refuse a
+ * schedule).  The front-end
  * entries (svsdf_check_sub_sw_collision, svsdf_shape_kernels) stay rigid, as in the reference.
  * The scaled path runs a reduced launch plan: solve widths 4 / 8 / 32, the launch chain only (no fused tail), no culls, and
  * every GSIP sample solved; svsdf_get_plan reports it.  The schedule belongs to the context: it survives svsdf_set_points /
@@ -767,6 +782,14 @@ typedef struct svsdf_scale {
 } svsdf_scale;
 int svsdf_set_scale(svsdf_ctx *ctx, const svsdf_scale *scale);
 int svsdf_get_scale(const svsdf_ctx *ctx, svsdf_scale *out);
+/* Host only, no context (the companion of svsdf_motion_bounds for the certified clearance under a schedule): rigorous bounds
+ *   out4 = { Smin = inf min_a s_a (rounded down), Smax = sup max_a s_a (rounded up),
+ *            Imax = sup max_a 1 / s_a (rounded up), Q = sup max_a |s_a'| / s_a^2 (rounded up) }     over t in [ta, tb],
+ * s_a' = A_a w_a cos(w_a t + phi_a).  The ranges of sin and |cos| over the argument interval [w_a ta + phi_a, w_a tb + phi_a]
+ * (widened by its own rounding) come from its endpoints and the extrema it contains; an interval a period long gives the
+ * full range.  NULL or enabled = 0 gives {1, 1, 1, 0}, and so does c = 1, amp = 0.  SVSDF_ERR_INVALID with a message: what
+ * svsdf_set_scale refuses, tb < ta, a NaN or infinite bound of the interval, a null out4. */
+int svsdf_scale_bounds(const svsdf_scale *scale, double ta, double tb, double out4[4]);
 
 /* Launch plan of the resident point set.  Every field only moves TIME: each setting returns the same bits (cost, gradient
  * and per-point results).  By default everything follows deterministic rules: the first evaluation

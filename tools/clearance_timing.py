@@ -14,7 +14,11 @@ svsdf_min_clearance without a target and svsdf_query_points on the same cloud: t
 figure of interest, and how many of the points svsdf_query_points reads clear (sdf > 0) the certified upper puts in
 collision (upper < 0).
 
-    python tools/clearance_timing.py [--steps 5] [--warmup 1] [--cases star sdHorseshoe sdHeart C3] [--per-point] [--out FILE]
+--scaled: the same cases under the reference's worked scale schedule (binding.EXAMPLE_SCALE) on a context created with
+FLAG_SCALED_CLEARANCE: the scaled search ("Under a scale schedule").  The lines carry "scaled": true
+and the schedule; svsdf_query_points beside them runs under the same schedule.  The rigid lines are the comparison.
+
+    python tools/clearance_timing.py [--steps 5] [--warmup 1] [--cases star sdHorseshoe sdHeart C3] [--per-point] [--scaled] [--out FILE]
 """
 import argparse
 import json
@@ -38,13 +42,13 @@ from svsdf_amd import workload  # noqa: E402
 ASSETS = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_assets.json")))
 
 
-def _case(name):
+def _case(name, flags=0):
     """(context, coeffs, T, number of points, safety_hor)"""
     if name == "C3":
         w = workload.make("C3", minco=svsdf_amd.minco_coeffs)
         kw = dict(safety_hor=w["safety_hor"], weight_p=w["weight_p"], rho=w["rho"], poly_params=w["poly_params"],
                   head_state=w["head_state"], tail_state=w["tail_state"], polygon=w["polygon"])
-        ctx = svsdf_amd.SvsdfContext(shape=w["shape"], device=0, **kw)
+        ctx = svsdf_amd.SvsdfContext(shape=w["shape"], device=0, flags=flags, **kw)
         ctx.set_points(w["points"])
         return ctx, w["coeffs"], w["T"], len(w["points"]), float(w["safety_hor"])
     w = workload.reference_case(name, N=24, iterates=1)
@@ -54,7 +58,7 @@ def _case(name):
     pts = c.min(axis=0) + (np.unique(np.floor((c - c.min(axis=0)) / res).astype(np.int64), axis=0) + 0.5) * res
     kw = dict(safety_hor=w["safety_hor"], weight_p=w["weight_p"], rho=w["rho"], poly_params=w["poly_params"],
               head_state=w["head_state"], tail_state=w["tail_state"])
-    ctx = svsdf_amd.SvsdfContext(shape=name, device=0, **kw)
+    ctx = svsdf_amd.SvsdfContext(shape=name, device=0, flags=flags, **kw)
     coeffs, T = ctx.lmbm_prepare(w["xs"][0])
     ctx.set_points(pts)
     return ctx, coeffs, T, len(pts), float(w["safety_hor"])
@@ -77,10 +81,15 @@ def main():
     ap.add_argument("--cases", nargs="+", default=["star", "sdHorseshoe", "sdHeart", "C3"])
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--per-point", action="store_true", help="time svsdf_point_clearance (see above)")
+    ap.add_argument("--scaled", action="store_true", help="under binding.EXAMPLE_SCALE on a FLAG_SCALED_CLEARANCE context")
     a = ap.parse_args()
     for name in a.cases:
-        ctx, coeffs, T, P, safety_hor = _case(name)
+        ctx, coeffs, T, P, safety_hor = _case(name, svsdf_amd.FLAG_SCALED_CLEARANCE if a.scaled else 0)
         row = {"case": name, "points": P, "pieces": len(T), "duration_s": float(np.sum(T)), "eps": 1e-3}
+        if a.scaled:
+            ctx.set_scale(**svsdf_amd.binding.EXAMPLE_SCALE)
+            row["scaled"] = True
+            row["schedule"] = svsdf_amd.binding.EXAMPLE_SCALE
         upper = None
         if a.per_point:
             row["mode"] = "per_point"
